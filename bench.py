@@ -13,7 +13,12 @@ bare with N > 1 it launches its N ranks itself as children (before importing tor
 rank 0's line and exits with their status.
 Inputs are synthetic and resident in HBM before the timed region.  Prints ONE JSON line (rank 0).
 
-JSON extras:
+A plain run sets up, warms up (W steps, then one more untimed step per kernel class -- the steps `--full` times class by
+class -- so that the timed steps are the same steps of the run in both modes), times the K steps and prints the line
+(`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, `config`).  `--full` adds the extras below.
+`--dump-outputs DIR` writes what the last timed step left to a caller of `sim_step!` as DIR/<name>.npy (see dump_outputs()).
+
+JSON extras (--full):
   roofline      the kernel class that takes most of a step (hipEvents on the library's stream inside the timed region):
                 `achieved` = the bytes the kernel HAS TO move per launch (its own operator's compulsory traffic: every
                 distinct array element it needs read once + written once; coefficient arrays are not needed in
@@ -197,6 +202,60 @@ def class_table(L):
     return names
 
 
+def roofline_extras(args, uniform_rows, dims, world, tsz, dominant, per_class, launches, cells, total_ms):
+    """--full: `roofline` (the dominant class, bracketed inside the timed region: its launches, cells and summed ms),
+    `smoother` and `prolong_increment` (from their one-step class timings) -- see the module docstring"""
+    n_uni, n_rows = uniform_rows
+    phi = n_uni / max(1, n_rows)                       # share of x-rows whose L / iD loads are skipped
+    cube = dims[0] == dims[1] == dims[2]
+    traffic_db = {}
+    tfile = os.path.join(ROOT, "profiles", "traffic.json")
+    if os.path.exists(tfile) and cube and world == 1 and args.layout == "padded":
+        try:
+            traffic_db = json.load(open(tfile))
+        except Exception:
+            traffic_db = {}
+
+    tkey = f"{dims[0]}^3/{args.dtype}" + ("" if args.body == "sphere" else "/" + args.body)   # case key of profiles/traffic.json
+
+    def kernel_record(nm, launches, cells, total_ms):
+        """bytes / rates of one kernel class from its launch count, summed cells and summed duration"""
+        if not launches or total_ms <= 0:
+            return None
+        dense, need, extra = ALG_T[nm]
+        avg_ms = total_ms / launches
+        cpl = cells / launches
+        need_b = (need + (1.0 - phi) * extra) * tsz * cpl
+        dense_b = dense * tsz * cpl
+        rate = need_b / (avg_ms * 1e-3) / 1e9
+        drate = dense_b / (avg_ms * 1e-3) / 1e9
+        rec = {"bound": "hbm", "kernel": nm, "achieved": rate, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": rate / HBM_PEAK_GBS,
+               "traffic": traffic_db.get(f"{nm}@{tkey}"), "launches": launches, "avg_launch_ms": avg_ms,
+               "algorithmic_bytes_per_launch": need_b,
+               "dense": {"bytes_per_launch": dense_b, "GB/s": drate, "frac_of_peak": drate / HBM_PEAK_GBS,
+                         "note": "SURVEY 8(d) per-cell figure of the reference operator; the fused kernel does not move these bytes"}}
+        if rec["traffic"]:
+            rec["traffic_GB/s"] = rec["traffic"] / (avg_ms * 1e-3) / 1e9
+            # a committed constant of an earlier rocprofv3 --pmc run of this command (tools/profile.sh), not measured by THIS run
+            rec["traffic_source"] = "profiles/" + str(traffic_db.get("_source", {}).get(tkey, "?")) + "_pmc_traffic_*"
+            rec["traffic_build_matches"] = traffic_db.get("_csrc_sha1", {}).get(tkey) == _csrc_digest()   # same kernel sources as profiled?
+        return rec
+
+    roof = kernel_record(dominant, launches, cells, total_ms)
+    if roof is None:   # the class had no finest-level launch in the timed region: say so instead of failing after the run
+        roof = {"bound": "hbm", "kernel": dominant, "achieved": None, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": None,
+                "traffic": None, "launches": int(launches), "note": "no finest-level launch of this class was timed"}
+    roof["uniform_row_fraction"] = phi
+    # (one extra step per class right after warm-up: a pcg! call that leaves early still enqueues its remaining kernels as
+    #  no-ops, so ms / launches here is NOT a per-kernel duration -- `avg_launch_ms` above and profiles/ are)
+    roof["per_class_ms_one_step"] = {k: {"launches": v["launches"], "ms": v["ms"]} for k, v in per_class.items()}
+    sm = per_class.get("smooth")
+    pr = per_class.get("prolongate")
+    return {"roofline": roof,
+            "smoother": kernel_record("smooth", sm["launches"], sm["cells"], sm["ms"]) if sm else None,
+            "prolong_increment": kernel_record("prolongate", pr["launches"], pr["cells"], pr["ms"]) if pr else None}
+
+
 C4_GRID = (1024, 1024, 512)   # BASELINE.json configs[3]: the strong-scaling case of the north star
 
 
@@ -234,7 +293,15 @@ def parse_args(argv=None):
     ap.add_argument("--no-ref1", action="store_true",
                     help="N>1 strong scaling: do not time the same global grid on ONE GPU (rank 0, after the N-GPU run) for `speedup_vs_1gpu`")
     ap.add_argument("--ref1-steps", type=int, default=5)
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also the extras of the line: per-class timing and roofline figures, the dense-layout leg (N=1), the "
+                         "one-GPU leg of a strong-scaling run (N>1) and the CPU baseline (N=1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write u, p, dt and the V-cycle counts of the last step to DIR/<name>.npy")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def self_launch_cmd(ngpus, port, argv):
@@ -290,6 +357,32 @@ def timed_steps(sim, steps, warmup, remeasure, sync):
         S.sim_step(sim, remeasure=remeasure)
     sync()
     return time.perf_counter() - t0
+
+
+DUMP_CELLS = 1 << 20    # --dump-outputs: grids with more cells are sampled (u and p of 2^20 cells: 32 MB in Float64)
+
+
+def dump_outputs(sim, out_dir, suffix=""):
+    """What a caller of `sim_step!` holds after the last timed step, as DIR/<name><suffix>.npy:
+      u        (cells..., D) and p (cells...): whole, ghost cells included, when the grid has at most DUMP_CELLS cells; else
+               the same fixed, seeded sample of DUMP_CELLS logical cells (i, j, k) of both, in any row layout
+      dt       every time step so far (Float64)
+      vcycles  V-cycles of the two pressure solves of the last step"""
+    import torch
+    from waterlily_amd import sim as S
+    os.makedirs(out_dir, exist_ok=True)
+    u, p = sim.flow.u, sim.flow.p
+    shape = tuple(p.shape)
+    ncell = int(np.prod(shape))
+    if ncell <= DUMP_CELLS:
+        hu, hp = S.to_host(u), S.to_host(p)
+    else:
+        flat = np.sort(np.random.default_rng(0).choice(ncell, DUMP_CELLS, replace=False, shuffle=False))
+        idx = tuple(torch.from_numpy(a).to(u.device) for a in np.unravel_index(flat, shape, order="F"))
+        hu, hp = u[idx].cpu().numpy(), p[idx].cpu().numpy()
+    arrays = {"u": hu, "p": hp, "dt": np.asarray(sim.flow.dt, np.float64), "vcycles": np.asarray(sim.pois.n[-2:], np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), a)
 
 
 def main(argv=None):
@@ -404,15 +497,19 @@ def main(argv=None):
     for w in range(args.warmup):
         S.sim_step(sim, remeasure=remeasure)
     sync()
-    # each finest-level class is timed in one extra warm-up step: finds the dominant kernel, feeds the smoother objects
-    classes = ["pcg_mult_dot", "pcg_update", "pcg_direction", "smooth", "prolongate", "conv_diff", "bdim", "residual", "correct",
-               "div", "cfl", "scale"]
-    per_class = {nm: timed_class(nm) for nm in classes if nm in names}
-    dominant = args.kernel or max(per_class, key=lambda k: per_class[k]["ms"])
-
-    # timed region: only the dominant class is bracketed by hipEvents (on the library's stream)
-    _lib.check(L.wl_prof_reset())
-    _lib.check(L.wl_prof_select(names[dominant], int(0.9 * ncell)))
+    # each finest-level class is timed in one extra warm-up step: finds the dominant kernel, feeds the smoother objects.
+    # A plain run takes the same steps untimed, so its timed steps are the same steps of the run as under --full.
+    classes = [nm for nm in ("pcg_mult_dot", "pcg_update", "pcg_direction", "smooth", "prolongate", "conv_diff", "bdim", "residual",
+                             "correct", "div", "cfl", "scale") if nm in names]
+    if args.full:
+        per_class = {nm: timed_class(nm) for nm in classes}
+        dominant = args.kernel or max(per_class, key=lambda k: per_class[k]["ms"])
+        # timed region: only the dominant class is bracketed by hipEvents (on the library's stream)
+        _lib.check(L.wl_prof_reset())
+        _lib.check(L.wl_prof_select(names[dominant], int(0.9 * ncell)))
+    else:
+        for _ in classes:
+            S.sim_step(sim, remeasure=remeasure)
     n0 = len(sim.pois.n)
     sync()
     t0 = time.perf_counter()
@@ -426,58 +523,10 @@ def main(argv=None):
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev if (args.comm == "rccl" and not real_rccl_sockets) else "cpu")
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
-    nl, nc, ms = C.c_int64(), C.c_int64(), C.c_double()
-    _lib.check(L.wl_prof_timed(C.byref(nl), C.byref(nc), C.byref(ms)))
-    _lib.check(L.wl_prof_select(-1, 0))
     vcycles = sim.pois.n[n0:]
-
+    if args.dump_outputs:
+        dump_outputs(sim, args.dump_outputs, "" if world == 1 else f"_rank{rank}")
     mlups = ncell_global * args.steps / elapsed / 1e6
-    n_uni, n_rows = S.uniform_rows(sim.pois, 0)
-    phi = n_uni / max(1, n_rows)                       # share of x-rows whose L / iD loads are skipped
-    cube = dims[0] == dims[1] == dims[2]
-    traffic_db = {}
-    tfile = os.path.join(ROOT, "profiles", "traffic.json")
-    if os.path.exists(tfile) and cube and world == 1 and args.layout == "padded":
-        try:
-            traffic_db = json.load(open(tfile))
-        except Exception:
-            traffic_db = {}
-
-    tkey = f"{dims[0]}^3/{args.dtype}" + ("" if args.body == "sphere" else "/" + args.body)   # case key of profiles/traffic.json
-
-    def kernel_record(nm, launches, cells, total_ms):
-        """bytes / rates of one kernel class from its launch count, summed cells and summed duration"""
-        if not launches or total_ms <= 0:
-            return None
-        dense, need, extra = ALG_T[nm]
-        avg_ms = total_ms / launches
-        cpl = cells / launches
-        need_b = (need + (1.0 - phi) * extra) * tsz * cpl
-        dense_b = dense * tsz * cpl
-        rate = need_b / (avg_ms * 1e-3) / 1e9
-        drate = dense_b / (avg_ms * 1e-3) / 1e9
-        rec = {"bound": "hbm", "kernel": nm, "achieved": rate, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": rate / HBM_PEAK_GBS,
-               "traffic": traffic_db.get(f"{nm}@{tkey}"), "launches": launches, "avg_launch_ms": avg_ms,
-               "algorithmic_bytes_per_launch": need_b,
-               "dense": {"bytes_per_launch": dense_b, "GB/s": drate, "frac_of_peak": drate / HBM_PEAK_GBS,
-                         "note": "SURVEY 8(d) per-cell figure of the reference operator; the fused kernel does not move these bytes"}}
-        if rec["traffic"]:
-            rec["traffic_GB/s"] = rec["traffic"] / (avg_ms * 1e-3) / 1e9
-            # a committed constant of an earlier rocprofv3 --pmc run of this command (tools/profile.sh), not measured by THIS run
-            rec["traffic_source"] = "profiles/" + str(traffic_db.get("_source", {}).get(tkey, "?")) + "_pmc_traffic_*"
-            rec["traffic_build_matches"] = traffic_db.get("_csrc_sha1", {}).get(tkey) == _csrc_digest()   # same kernel sources as profiled?
-        return rec
-
-    roof = kernel_record(dominant, nl.value, nc.value, ms.value)
-    if roof is None:   # the class had no finest-level launch in the timed region: say so instead of failing after the run
-        roof = {"bound": "hbm", "kernel": dominant, "achieved": None, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": None,
-                "traffic": None, "launches": int(nl.value), "note": "no finest-level launch of this class was timed"}
-    roof["uniform_row_fraction"] = phi
-    # (one extra step per class right after warm-up: a pcg! call that leaves early still enqueues its remaining kernels as
-    #  no-ops, so ms / launches here is NOT a per-kernel duration -- `avg_launch_ms` above and profiles/ are)
-    roof["per_class_ms_one_step"] = {k: {"launches": v["launches"], "ms": v["ms"]} for k, v in per_class.items()}
-    sm = per_class.get("smooth")
-    pr = per_class.get("prolongate")
     Re = {"sphere": 3700, "tgv": 1600}.get(args.body, 1000)
     what = ("uniform inflow, remeasure=false" if args.body in ("sphere", "donut") else
             ("body moving through fluid at rest, remeasure=true (native measure! + changed-rows update! every step)" if remeasure else "no body"))
@@ -503,10 +552,12 @@ def main(argv=None):
                                                                    ("ncclAllReduce" if args.comm == "rccl" else ("device scaling" if loopback else "host callbacks")))),
                    "collectives_last_step": S.comm_counts() if world > 1 else None,
                    "vcycles_per_solve": vcycles[:6], "mean_vcycles_per_step": float(np.sum(vcycles)) / args.steps},
-        "roofline": roof,
-        "smoother": kernel_record("smooth", sm["launches"], sm["cells"], sm["ms"]) if sm else None,
-        "prolong_increment": kernel_record("prolongate", pr["launches"], pr["cells"], pr["ms"]) if pr else None,
     }
+    if args.full:
+        nl, nc, ms = C.c_int64(), C.c_int64(), C.c_double()
+        _lib.check(L.wl_prof_timed(C.byref(nl), C.byref(nc), C.byref(ms)))
+        _lib.check(L.wl_prof_select(-1, 0))
+        out.update(roofline_extras(args, S.uniform_rows(sim.pois, 0), dims, world, tsz, dominant, per_class, nl.value, nc.value, ms.value))
     if loopback and world > 1:
         # value = what `world` such ranks would deliver if nothing but this rank's own work limited them (no wire time)
         stalled = max(vcycles) >= 32 if vcycles else False
@@ -523,7 +574,7 @@ def main(argv=None):
     import gc
     gc.collect()
     torch.cuda.empty_cache()
-    if world == 1 and not args.no_dense_leg and args.layout == "padded":
+    if args.full and world == 1 and not args.no_dense_leg and args.layout == "padded":
         # the layout the reference-side binding hands over (julia/WaterLilyHIPNativeExt.jl: dense column-major, pitch N+2)
         try:
             sd = make_sim(args, dims, T, dev, False)
@@ -540,7 +591,7 @@ def main(argv=None):
     if real:
         wd.finalize()
         dist.destroy_process_group()          # (before rank 0's one-GPU leg: nobody waits in a collective for it)
-    if real and scaling == "strong" and not args.no_ref1 and rank == 0:
+    if args.full and real and scaling == "strong" and not args.no_ref1 and rank == 0:
         # the same global grid on ONE GPU (rank 0's, the communicator is gone): the denominator of the strong-scaling claim
         try:
             s1 = make_sim(args, dims, T, dev, args.layout == "padded")
@@ -554,7 +605,7 @@ def main(argv=None):
         except Exception as e:
             out["one_gpu"] = {"error": str(e)[:200]}
             out["speedup_vs_1gpu"] = None
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         out["cpu_baseline"] = cpu_baseline(args.cpu_size, args.cpu_steps, args.cpu_c1_steps)
     if rank == 0 or loopback:
         print(json.dumps(out), flush=True)

@@ -48,6 +48,18 @@ def test_bench_self_launch_command_and_defaults():
     assert a.size is None and a.grid is None and not a.weak and bench.C4_GRID == (1024, 1024, 512)
 
 
+def test_bench_plain_run_is_the_default_and_steps_are_checked():
+    """the extras of the line are asked for with --full; --steps is the number of timed steps and has to be one at least"""
+    sys.path.insert(0, ROOT)
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert not a.full and a.dump_outputs is None and (a.steps, a.warmup) == (7, 3)
+    assert bench.parse_args(["--full", "--dump-outputs", "d"]).full and bench.parse_args(["--dump-outputs", "d"]).dump_outputs == "d"
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit):
+            bench.parse_args(bad)
+
+
 def test_bench_parent_stays_off_the_gpu_and_relays_the_ranks_status():
     """Without a GPU the two ranks fail; the parent (which must not import torch before it decides to launch) reports
     their failure with a non-zero exit and prints no result line."""
@@ -80,11 +92,45 @@ def test_torch_free_host_reproduces_the_golden_steps(name, layout):
 
 
 @pytest.mark.gpu
+def test_bench_plain_and_full_runs_take_the_same_steps_and_dump_them(tmp_path):
+    """One GPU: a plain run prints the headline line without the --full extras; --full adds them.  Both take the same steps
+    (the per-class steps of --full are untimed warm-up steps of a plain run) and --dump-outputs writes what the last one left:
+    at 128^3 (more cells than bench.DUMP_CELLS) a seeded sample of u and p, the same cells in both runs."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+
+    def run(d, *extra):
+        r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--size", "128", "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", str(d), *extra], capture_output=True, text=True, env=_env(), cwd=ROOT, timeout=900)
+        assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+        out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')][-1])
+        files = sorted(os.listdir(d))
+        assert files == ["dt.npy", "p.npy", "u.npy", "vcycles.npy"], files
+        assert sum(os.path.getsize(os.path.join(d, f)) for f in files) <= 64 << 20
+        return out, {f[:-4]: np.load(os.path.join(d, f)) for f in files}
+
+    extras = ("roofline", "smoother", "prolong_increment", "layout_dense", "cpu_baseline")
+    plain, a = run(tmp_path / "plain")
+    assert plain["steps"] == 3 and plain["ms_per_step"] > 0 and plain["value"] > 0 and plain["higher_is_better"] is True
+    assert plain["unit"] == "MLUPS" and plain["dtype"] == "f32" and not any(k in plain for k in extras)
+    assert a["u"].dtype == np.float32 and a["u"].shape[1] == 3 and len(a["u"]) == len(a["p"]) == bench.DUMP_CELLS
+    assert a["dt"].dtype == np.float64 and len(a["vcycles"]) == 2 and np.all(np.isfinite(a["u"])) and np.all(np.isfinite(a["p"]))
+    full, b = run(tmp_path / "full", "--full", "--cpu-size", "32", "--cpu-steps", "1", "--cpu-c1-steps", "2")
+    assert all(k in full for k in extras) and full["roofline"]["kernel"] in bench.ALG_T
+    assert full["layout_dense"]["ms_per_step"] > 0 and full["cpu_baseline"]["value"] > 0
+    assert len(b["dt"]) == len(a["dt"]) and np.array_equal(b["vcycles"], a["vcycles"])
+    for k in ("u", "p"):
+        scale = float(np.max(np.abs(a[k])))
+        assert np.allclose(b[k], a[k], rtol=1e-4, atol=1e-5 * scale), (k, float(np.max(np.abs(b[k] - a[k]))))
+
+
+@pytest.mark.gpu
 def test_bench_launches_its_own_ranks():
     """`python bench.py --gpus 2` with no launcher around it (the two ranks share the test GPU over the host transport): one
     JSON line, two ranks, strong scaling on the stated grid, the one-GPU time of the same grid and the speed-up in the line."""
     r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--comm", "host", "--size", "64", "--steps", "2", "--warmup", "1",
-                        "--ref1-steps", "2"], capture_output=True, text=True, env=_env(), cwd=ROOT, timeout=900)
+                        "--ref1-steps", "2", "--full"], capture_output=True, text=True, env=_env(), cwd=ROOT, timeout=900)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')]
     assert len(lines) == 1
@@ -101,7 +147,8 @@ def test_bench_rccl_path_between_two_processes():
     all-gathers, the communicator assertion, rank 0's one-GPU leg after the communicator is gone) between two real processes on the
     one GPU of the box: they present themselves to RCCL as two hosts, so it pairs them over sockets (WL_RCCL_OVER_SOCKETS=1)."""
     env = dict(_env(), WL_RCCL_OVER_SOCKETS="1")
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--size", "64", "--steps", "2", "--warmup", "1", "--ref1-steps", "2"],
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--size", "64", "--steps", "2", "--warmup", "1", "--ref1-steps", "2",
+                        "--full"],
                        capture_output=True, text=True, env=env, cwd=ROOT, timeout=900)
     if r.returncode != 0 and "RCCL communicator failed" in r.stderr and '{"metric"' not in r.stdout:
         pytest.skip("RCCL could not pair two ranks on one GPU over sockets on this box: " + r.stderr[-600:])

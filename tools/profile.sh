@@ -16,11 +16,11 @@ esac
 OUT=$ROOT/gpurun_out/prof_${TAG}_$CASE
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o trace -- python3 $ROOT/bench.py --steps 10 --warmup 5 --no-cpu-baseline $ARGS > $OUT/${TAG}_bench_$LABEL.json 2> $OUT/trace.log
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o trace -- python3 $ROOT/bench.py --full --steps 10 --warmup 5 --no-cpu-baseline $ARGS > $OUT/${TAG}_bench_$LABEL.json 2> $OUT/trace.log
 python3 $ROOT/profiles/summarize_trace.py $OUT/trace_kernel_trace.csv 27 > $OUT/${TAG}_kernel_trace_summary_$LABEL.txt
 cp $OUT/trace_kernel_stats.csv $OUT/${TAG}_kernel_stats_$LABEL.csv
-rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT -o fetch -- python3 $ROOT/bench.py --steps 2 --warmup 5 --no-cpu-baseline $ARGS > $OUT/bench_fetch.json 2> $OUT/fetch.log
-rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT -o write -- python3 $ROOT/bench.py --steps 2 --warmup 5 --no-cpu-baseline $ARGS > $OUT/bench_write.json 2> $OUT/write.log
+rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT -o fetch -- python3 $ROOT/bench.py --full --steps 2 --warmup 5 --no-cpu-baseline $ARGS > $OUT/bench_fetch.json 2> $OUT/fetch.log
+rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT -o write -- python3 $ROOT/bench.py --full --steps 2 --warmup 5 --no-cpu-baseline $ARGS > $OUT/bench_write.json 2> $OUT/write.log
 cd $ROOT
 python3 profiles/parse_pmc.py $OUT/fetch_counter_collection.csv $OUT/write_counter_collection.csv "$KEY" $TAG > $OUT/${TAG}_pmc_traffic_$LABEL.txt
 cp profiles/traffic.json $OUT/traffic.json
