@@ -14,6 +14,7 @@ part of the default `-m gpu` run, each on ONE GPU:
   * hydrostatic pressure_force on the body = its volume (maintests.jl:341-346 in 3-D);
   * the traffic-saving kernel forms and the rows-per-thread variants do not change a bit;
   * two steps of the configuration itself: few V-cycles per solve, r.r < tol, div(u) = 0 to the solver tolerance.
+  * the operators against the extended-precision reference tests/xref.py at ~2^19 sampled cells of the bench case.
 
 WL_FULLSIZE selects cases by id (comma separated, default: all four)."""
 import gc
@@ -23,6 +24,9 @@ import os
 import numpy as np
 import pytest
 import torch
+
+import xref as X
+import xref_inputs as XI
 
 pytestmark = pytest.mark.gpu
 
@@ -215,13 +219,159 @@ def test_traffic_saving_switches_do_not_change_a_bit(S, case):
         assert float((a[3] - c[3]).abs().max()) <= 1e-10 * float(a[3].abs().max())
 
 
-def test_hydrostatic_force_and_two_steps_of_the_configuration(S, case):
+@pytest.fixture(scope="module")
+def bench_sim(S, case):
+    """the bench case (bench.py's set-up, with its body), built once per case and shared by the tests below"""
+    dims, T, kind = case
+    sim = _bench_case(dims, T, kind)
+    yield sim
+    del sim
+    gc.collect()
+    torch.cuda.empty_cache()
+
+
+def _worst(name, got, v, M, T):
+    w = X.worst(got, v, M, T)
+    assert w <= X.K[name], f"{name}: |hip-ref| = {w:.3g} eps*M > K = {X.K[name]}"
+    return w
+
+
+def _fails(name, got, v, M, T):
+    return X.worst(got, v, M, T) > X.K[name]
+
+
+def test_operators_against_the_extended_precision_reference_at_sampled_cells(S, case, bench_sim):
+    """tests/xref.py at full size, on the bench case with its body: D / iD against set_diag! from L, mult of a random x,
+    conv_diff! of a non-uniform u (smooth part + noise), restrictL! into level 1, one pcg! iteration from a known r with
+    x = 0 (alpha read back as x1/eps against (r0.z0)/(eps.A eps) summed in float64 on the device, r1 at the samples), and
+    dot / L2 / L∞ of the level arrays.  Compared at ~2^19 cells (conv_diff!: ~2^16), gathered on the device by flat index:
+    random cells, the x rows of planes k = 1, 2, mid, N-1, N, four whole z columns (every z-chunk seam) and the last row
+    of the last plane, the highest addresses.  Controls: samples shifted one plane, nu off by 64K eps, a dropped partial.
+    Every field it writes is restored, so the next test starts from the freshly built case."""
+    dims, T, kind = case
+    sim = bench_sim
+    ml, fl = sim.pois, sim.flow
+    lv, l1 = ml.levels[0], ml.levels[1]
+    Ng = tuple(n + 2 for n in dims)
+    ins = (slice(1, -1),) * 3
+    saved = {k: S.copy_of(getattr(lv, k)) for k in ("x", "r", "eps", "z")}
+    try:
+        idx = XI.samples(Ng, 1 << 18, 7, row_step=max(1, Ng[0] * Ng[1] * 5 // (1 << 18)))
+        sh = (idx[0], idx[1], np.minimum(idx[2] + 1, Ng[2] - 2))
+        # D / iD
+        C = XI.device_cells({"L": lv.L, "D": lv.D, "iD": lv.iD}, idx, Ng)
+        Dv, DM = X.diag(C)
+        _worst("diag", C("D"), Dv, DM, T)
+        iv, iM = X.inv_diag(Dv, DM, T)
+        _worst("iD", C("iD"), iv, iM, T)
+        assert np.any(C("iD") == 0) and np.any(C("iD") != 0)     # samples inside the body and in the fluid
+        # mult of a random x
+        x = lv.layout.alloc((), "cuda:0")
+        x[ins] = rand_like(x[ins], 21)
+        z = S.mult(ml, x)
+        C = XI.device_cells({"L": lv.L, "D": lv.D, "x": x, "z": z}, idx, Ng)
+        v, M = X.mult(C)
+        _worst("mult", C("z"), v, M, T)
+        Cs = XI.device_cells({"L": lv.L, "D": lv.D, "x": x}, sh, Ng)
+        assert _fails("mult", C("z"), *X.mult(Cs), T)
+        del x
+        # conv_diff! of u = U + smooth part + noise
+        un, out = S.like(fl.u), S.like(fl.u)
+        kk = torch.arange(Ng[2], device="cuda", dtype=torch.float64)
+        for i in range(3):
+            un[..., i] = (0.5 * torch.sin(2 * math.pi * (i + 1) * kk / Ng[2])).to(un.dtype)[None, None, :]
+            un[..., i] += 0.1 * rand_like(un[..., i], 30 + i)
+        nu = float(np.dtype(T).type(fl.nu))
+        S.conv_diff(out, un, nu=nu)
+        cidx = tuple(a[:: max(1, len(a) >> 16)] for a in idx)
+        csh = (cidx[0], cidx[1], np.minimum(cidx[2] + 1, Ng[2] - 2))
+        C = XI.device_cells({"u": un, "r": out}, cidx, Ng)
+        Cs = XI.device_cells({"u": un}, csh, Ng)
+        for c in range(3):
+            v, M = X.conv_diff(C, c, nu)
+            got = C("r", (), c)
+            _worst("conv_diff", got, v, M, T)
+            if c == 0:
+                assert _fails("conv_diff", got, *X.conv_diff(C, c, nu * (1 + 64 * X.K["conv_diff"] * X.eps(T))), T)
+                assert _fails("conv_diff", got, *X.conv_diff(Cs, c, nu), T)
+        del un, out
+        # restrictL! into level 1
+        aL = S.like(l1.L)
+        S.restrictL(aL, lv.L)
+        Nc = tuple(int(n) for n in l1.L.shape[:3])
+        cidx = XI.samples(Nc, 1 << 16, 8)
+        C = XI.device_cells({"b": lv.L, "a": aL}, cidx, Nc, NA=Ng)
+        for c in range(3):
+            v, M = X.restrictL(C, c)
+            _worst("restrictL", C("a", (), c), v, M, T)
+        del aL
+        # one pcg! iteration (it = 1) from x = 0 and a known r (ghost cells 0)
+        lv.x.zero_()
+        lv.eps.zero_()
+        lv.r.zero_()
+        lv.r[ins] = rand_like(lv.r[ins], 22)
+        r0 = S.copy_of(lv.r)
+        assert S.pcg(ml, it=1, level=0) == 1
+        e = lv.eps.double()
+        Ae = lv.D[ins].double() * e[ins]
+        MAe = (lv.D[ins].double() * e[ins]).abs()
+        for i in range(3):
+            lo = tuple(slice(0, -2) if d == i else slice(1, -1) for d in range(3))
+            hi = tuple(slice(2, None) if d == i else slice(1, -1) for d in range(3))
+            Li = lv.L[..., i].double()
+            a, b = e[lo] * Li[ins], e[hi] * Li[hi]
+            Ae += a + b
+            MAe += a.abs() + b.abs()
+            del Li, a, b
+        rho = float((r0.double()[ins] * e[ins]).sum())
+        Mrho = 2 * float((r0.double()[ins] * e[ins]).abs().sum())
+        ze = float((Ae * e[ins]).sum())
+        Mze = 2 * float((MAe * e[ins].abs()).sum())
+        del e, Ae, MAe
+        al = rho / ze
+        Ma = abs(al) * (Mrho / abs(rho) + Mze / abs(ze))
+        C = XI.device_cells({"x": lv.x, "eps": lv.eps, "r": lv.r, "r0": r0, "L": lv.L, "D": lv.D}, idx, Ng)
+        ev = C("eps")
+        nz = ev != 0
+        a_hip = np.asarray(C("x")[nz] / ev[nz], np.float64)
+        _worst("alpha", a_hip, np.full(nz.sum(), al), np.full(nz.sum(), Ma), T)
+        assert _fails("alpha", a_hip, np.full(nz.sum(), al * (1 + 64 * X.K["alpha"] * Ma / abs(al) * X.eps(T))),
+                      np.full(nz.sum(), Ma), T)
+        zv, zM = X.mult(C, "eps")
+        r0v = C("r0")
+        _worst("pcg", C("r"), r0v - X.LD(al) * zv, abs(r0v) + X.LD(abs(al)) * zM + X.LD(Ma) * abs(zv), T)
+        # dot / L2 / L∞ of the level arrays against float64 sums on the device
+        got = S.dot(lv.r, lv.eps)
+        ref = float((lv.r.double() * lv.eps.double()).sum())
+        Mref = float((lv.r.double() * lv.eps.double()).abs().sum())
+        n = float(np.prod(Ng))
+        tol = (lambda v: float(np.spacing(np.float32(abs(v))))) if np.dtype(T) == np.float32 else \
+            (lambda v: 4 * math.log2(n) * X.eps(T) * Mref)
+        assert abs(got - ref) <= tol(ref)
+        big = float((lv.r.double() * lv.eps.double()).abs().max())
+        assert abs(got - (ref - big)) > tol(ref)                   # control: one partial dropped
+        r2 = float((lv.r.double() ** 2).sum())
+        assert abs(S.L2p(ml) - r2) <= (float(np.spacing(np.float32(r2))) if np.dtype(T) == np.float32
+                                        else 4 * math.log2(n) * X.eps(T) * r2)
+        assert S.Linf(ml) == float(lv.r.abs().max())
+        m = 2 * float(lv.r.abs().max())
+        lv.r[-2, -2, -2] = -m                                      # unique maximum, negative, in the last inside cell
+        assert S.Linf(ml) == m
+        lv.r[-1, -1, -1] = -2 * m                                  # and in the last ghost cell, the highest address
+        assert S.Linf(ml) == 2 * m
+        del r0
+    finally:
+        for k, a in saved.items():
+            getattr(lv, k).copy_(a)
+
+
+def test_hydrostatic_force_and_two_steps_of_the_configuration(S, case, bench_sim):
     """The BASELINE configuration itself (bench.py's set-up), two `sim_step!`s from the impulsive start: every solve
     converges in a few V-cycles (the reference's own multigrid bound is n <= 3 on its manufactured problems,
     maintests.jl:112-115; an impulsive start with a body takes one or two more on the first solve), leaves r.r below the
     solver tolerance and a velocity field that is divergence-free to it; forces, dt and u stay finite."""
     dims, T, kind = case
-    sim = _bench_case(dims, T, kind)
+    sim = bench_sim
     # maintests.jl:341-346 in 3-D at full size first, through the whole product path (measure! on the device, the |d| <= 1 band
     # rebuilt from its band cells, wl_pforce): p = y  =>  force = displaced volume * e_y
     m = min(dims)

@@ -1,0 +1,240 @@
+"""The CPU oracle (oracle/wlo_impl.h, scatter form, rounds like the reference) against the independent extended-precision
+reference tests/xref.py (gather form, no rounding), operator by operator, on the adversarial inputs of xref_inputs.py:
+|oracle - ref| <= K * eps_T * M at every cell, K stated per operator (xref.py explains M).  Each comparison also carries a
+negative control: the same check against a reference with one planted error must FAIL."""
+import numpy as np
+import pytest
+
+import xref as X
+from oracle import wl_oracle as O
+from xref_inputs import KINDS, coefficients, field
+
+TYPES = [np.float32, np.float64]
+K = X.K
+WORST = {}
+
+
+def check(name, got, v, M, T, key=None, control=True):
+    """the comparison, and its control: the same values against the reference of the NEXT sample must fail"""
+    w = X.worst(got, v, M, T)
+    WORST[key or name] = max(WORST.get(key or name, 0.0), w)
+    assert w <= K[name], f"{name}: |got-ref| = {w:.3g} eps*M > K = {K[name]}"
+    assert not control or X.worst(got[:-1], v[1:], M[1:], T) > K[name], f"{name}: control (samples shifted by one) did not fail"
+    return w
+
+
+def fails(name, got, v, M, T):
+    return X.worst(got, v, M, T) > K[name]
+
+
+CD_CASES = [((10, 9), ()), ((10, 9), (0,)), ((7, 6, 5), ()), ((7, 6, 5), (0, 1, 2)), ((6, 5, 3), (2,)), ((5, 4, 3), ())]
+
+
+@pytest.mark.parametrize("T", TYPES)
+@pytest.mark.parametrize("Ng,perdir", CD_CASES)
+@pytest.mark.parametrize("kind", KINDS)
+def test_conv_diff_oracle_vs_xref(T, Ng, perdir, kind):
+    """conv_diff! with the ϕuL/ϕuR boundary faces and the periodic ϕuP face, nu = 0.3 (K = 8)"""
+    D = len(Ng)
+    u = field(Ng + (D,), T, kind, 1, seam=3)
+    nu = float(np.dtype(T).type(0.3))
+    r, Phi = O.zeros(Ng + (D,), T), O.zeros(Ng, T)
+    O.conv_diff(r, u, Phi, nu=nu, perdir=perdir)
+    C = X.host_cells({"u": u}, N=Ng)
+    for c in range(D):
+        v, M = X.conv_diff(C, c, nu, perdir)
+        got = r[..., c].ravel(order="F")
+        check("conv_diff", got, v, M, T, f"conv_diff {np.dtype(T).name}")
+        if kind == "random":                                   # negative controls
+            assert fails("conv_diff", got, *X.conv_diff(C, c, nu * (1 + 64 * K["conv_diff"] * X.eps(T)), perdir), T)
+            sh = X.host_cells({"u": u}, idx=tuple(a + (q == D - 1) for q, a in enumerate(C.idx)), N=Ng)
+            in_ = C.idx[D - 1] < Ng[D - 1] - 1
+            vs, Ms = X.conv_diff(sh, c, nu, perdir)
+            assert fails("conv_diff", got[in_], vs[in_], Ms[in_], T)
+
+
+@pytest.mark.parametrize("T", TYPES)
+@pytest.mark.parametrize("Ng", [(10, 9), (7, 6, 5)])
+@pytest.mark.parametrize("kind", KINDS)
+def test_flow_pointwise_operators_oracle_vs_xref(T, Ng, kind):
+    """div (K = 4), BDIM! (f: K = 4, u: K = 8), flux_out (K = 4)"""
+    D = len(Ng)
+    a = O.Flow(tuple(n - 2 for n in Ng), (1.0,) + (0.0,) * (D - 1), T=T, nu=0.01)
+    for q, k in enumerate(("u", "u0", "f", "V", "mu0", "mu1")):
+        getattr(a, k)[...] = field(getattr(a, k).shape, T, kind, 10 + q)
+    h = {k: getattr(a, k).copy(order="F") for k in ("u", "u0", "f", "V", "mu0", "mu1")}
+    C = X.host_cells(h, N=Ng)
+    ins = np.all([(x >= 1) & (x <= n - 2) for x, n in zip(C.idx, Ng)], axis=0)
+    z = O.zeros(Ng, T)
+    O._fn("wlo_div", T)(O._p(z), O._p(a.u), O.C.byref(a.grid))
+    v, M = X.div(C)
+    check("div", z.ravel(order="F")[ins], v[ins], M[ins], T, f"div {np.dtype(T).name}")
+    a.sigma[...] = 0
+    O.CFL(a)
+    v, M = X.flux_out(C)
+    check("flux_out", a.sigma.ravel(order="F")[ins], v[ins], M[ins], T, f"flux_out {np.dtype(T).name}")
+    dt = a.dt[-1]
+    O.BDIM(a)
+    for c in range(D):
+        v, M = X.bdim_f(C, c, dt)
+        check("bdim_f", a.f[..., c].ravel(order="F"), v, M, T, f"bdim_f {np.dtype(T).name}")
+        v, M = X.bdim_u(C, c, dt)
+        got = a.u[..., c].ravel(order="F")
+        check("bdim_u", got[ins], v[ins], M[ins], T, f"bdim_u {np.dtype(T).name}")
+        if kind == "random":
+            assert fails("bdim_u", got[ins], *[q[ins] for q in X.bdim_u(C, c, dt * (1 + 64 * K["bdim_u"] * X.eps(T)))], T)
+
+
+def poisson(Ng, T, seed, Lkind="body", edge=None, rkind="random"):
+    D = len(Ng)
+    L = coefficients(Ng, T, seed, Lkind, edge, seam=3)
+    x = field(Ng, T, rkind, seed + 1)
+    z = field(Ng, T, rkind, seed + 2)
+    return O.Poisson(x.copy(order="F"), L.copy(order="F"), z.copy(order="F")), L, x, z
+
+
+P_SHAPES = [(10, 9), (9, 8, 7), (6, 5, 3)]
+
+
+@pytest.mark.parametrize("T", TYPES)
+@pytest.mark.parametrize("Ng", P_SHAPES)
+@pytest.mark.parametrize("Lkind,edge", [("body", None), ("row", "f1"), ("row", "n-1"), ("row", "y")])
+def test_poisson_operators_oracle_vs_xref(T, Ng, Lkind, edge):
+    """set_diag! (D: K = 4, iD: K = 8, iD == 0 exactly on the solid cells), mult (K = 4), residual! (K = 8 after the
+    mean shift), Jacobi!+increment! (K = 8)"""
+    p, L, x, z = poisson(Ng, T, 3, Lkind, edge)
+    tn = np.dtype(T).name
+    C = X.host_cells({"L": L, "D": p.D, "iD": p.iD, "x": x, "z": z}, N=Ng)
+    ins = np.all([(q >= 1) & (q <= n - 2) for q, n in zip(C.idx, Ng)], axis=0)
+    Dv, DM = X.diag(C)
+    check("diag", p.D.ravel(order="F")[ins], Dv[ins], DM[ins], T, f"diag {tn}")
+    iv, iM = X.inv_diag(Dv, DM, T)
+    check("iD", p.iD.ravel(order="F")[ins], iv[ins], iM[ins], T, f"iD {tn}")
+    if Lkind == "body":
+        assert np.any(p.iD[O.inside(p.iD)] == 0)
+    # mult: z = A x (ghosts 0)
+    xr = field(Ng, T, "random", 30)
+    Cx = X.host_cells({"L": L, "D": p.D, "x": xr}, N=Ng)
+    zz = O.mult(p, xr.copy(order="F")).ravel(order="F")
+    v, M = X.mult(Cx)
+    check("mult", zz[ins], v[ins], M[ins], T, f"mult {tn}")
+    assert np.all(zz[~ins] == 0)
+    Lp = L.copy(order="F")                                      # control: one face coefficient off by 64K eps, at the
+    xm = np.roll(xr, 1, axis=0).ravel(order="F").astype(np.float64)     # cell where that face weighs most in M
+    Mf = np.asarray(M, np.float64)
+    w = np.where(ins & (C.idx[0] >= 2) & (Mf > 0), np.abs(xm * L[..., 0].ravel(order="F")) / np.where(Mf > 0, Mf, 1), 0)
+    q = int(np.argmax(w))
+    I = tuple(int(a[q]) for a in C.idx)
+    Lp[I + (0,)] *= 1 + 64 * K["mult"] * X.eps(T)
+    Cp = X.host_cells({"L": Lp, "D": p.D, "x": xr}, N=Ng)
+    assert fails("mult", zz[ins], *[q[ins] for q in X.mult(Cp)], T)
+    # residual!
+    p.z[...] = z
+    O.residual(p)
+    rv, rM = X.residual_local(C)
+    n_in = int(np.prod([n - 2 for n in Ng]))
+    s = sum(float(q) for q in rv[ins]) / n_in
+    sM = sum(float(q) for q in rM[ins]) / n_in
+    if abs(s) > 4 * X.eps(T):
+        rv, rM = rv - X.LD(s), rM + X.LD(sM)
+    check("residual", p.r.ravel(order="F")[ins], rv[ins], rM[ins], T, f"residual {tn}")
+    # Jacobi! + increment!
+    r0, x0 = p.r.copy(order="F"), x.copy(order="F")
+    Cj = X.host_cells({"L": L, "D": p.D, "iD": p.iD, "r": r0, "x": x0}, N=Ng)
+    O.Jacobi(p)
+    (ev, eM), (rv, rM), (xv, xM) = X.jacobi_increment(Cj)
+    check("jacobi", p.eps.ravel(order="F")[ins], ev[ins], eM[ins], T, f"jacobi {tn}")
+    check("jacobi", p.r.ravel(order="F")[ins], rv[ins], rM[ins], T, f"jacobi {tn}")
+    check("jacobi", p.x.ravel(order="F")[ins], xv[ins], xM[ins], T, f"jacobi {tn}")
+
+
+@pytest.mark.parametrize("T", TYPES)
+@pytest.mark.parametrize("Ng", P_SHAPES)
+def test_pcg_one_iteration_and_exits_oracle_vs_xref(T, Ng):
+    """pcg!(it=1) from x = 0: alpha read back as x1/eps (K = 16), x1 and r1 = r0 - alpha*A*eps (K = 16); the exits of
+    Poisson.jl:127 (|rho| < 10eps: r = 0) and :132 (|alpha| > 100: eps in the near-null space of A) change nothing."""
+    p, L, x, z = poisson(Ng, T, 5)
+    r = field(Ng, T, "random", 8)
+    r[tuple(np.setdiff1d(np.arange(n), np.arange(1, n - 1)) for n in Ng[:1]) + (slice(None),) * (len(Ng) - 1)] = 0
+    r = np.asfortranarray(r)
+    for d in range(len(Ng)):                                    # ghost cells of r are 0 (outside(p.r) ≡ 0, Poisson.jl:146)
+        idx = [slice(None)] * len(Ng)
+        idx[d] = [0, Ng[d] - 1]
+        r[tuple(idx)] = 0
+    p.x[...] = 0
+    p.r[...] = r
+    p.eps[...] = 0
+    (al, Ma), _, _, x1, r1, ins = X.pcg1_ref(L, p.D.copy(order="F"), p.iD.copy(order="F"), r)
+    assert O.pcg(p, it=1) == 1
+    tn = np.dtype(T).name
+    e = p.eps.ravel(order="F")
+    sel = ins & (np.abs(e) > 0)
+    check("alpha", p.x.ravel(order="F")[sel] / e[sel].astype(np.float64), np.full(sel.sum(), al), np.full(sel.sum(), Ma), T,
+          f"alpha {tn}", control=False)          # (a scalar: its control is the planted error below)
+    check("pcg", p.x.ravel(order="F")[ins], x1[0][ins], x1[1][ins], T, f"pcg x {tn}")
+    check("pcg", p.r.ravel(order="F")[ins], r1[0][ins], r1[1][ins], T, f"pcg r {tn}")
+    assert fails("alpha", p.x.ravel(order="F")[sel] / e[sel].astype(np.float64),
+                 np.full(sel.sum(), al * (1 + 64 * K["alpha"] * X.eps(T) * float(Ma / abs(al)))), np.full(sel.sum(), Ma), T)
+    # exit :127 -- r = 0
+    p.x[...] = x
+    p.r[...] = 0
+    assert O.pcg(p, it=1) == 0 and np.array_equal(p.x, x)
+    # exit :132 -- r = c*D: eps = r*iD is constant up to rounding, A eps ~ 0, alpha huge
+    r2 = np.where(p.iD != 0, p.D, 0).astype(T)
+    p.r[...] = r2
+    p.x[...] = x
+    (al2, _), *_ = X.pcg1_ref(L, p.D.copy(order="F"), p.iD.copy(order="F"), np.asfortranarray(r2))
+    assert abs(al2) > 1e2
+    assert O.pcg(p, it=1) == 0 and np.array_equal(p.x, x) and np.array_equal(p.r, r2)
+
+
+@pytest.mark.parametrize("T", TYPES)
+@pytest.mark.parametrize("Ng", [(10, 10), (10, 8, 6)])
+def test_multilevel_transfers_oracle_vs_xref(T, Ng):
+    """restrict! (K = 4), restrictL! (K = 4, BC! planes included), prolongate! (exact)"""
+    D = len(Ng)
+    Nc = tuple(1 + n // 2 for n in Ng)
+    b = field(Ng, T, "random", 40)
+    a = O.zeros(Nc, T)
+    O.restrict(a, b)
+    C = X.host_cells({"b": b}, N=Nc, NA=Ng)
+    ins = np.all([(q >= 1) & (q <= n - 2) for q, n in zip(C.idx, Nc)], axis=0)
+    v, M = X.restrict(C)
+    check("restrict", a.ravel(order="F")[ins], v[ins], M[ins], T, f"restrict {np.dtype(T).name}")
+    L = coefficients(Ng, T, 41)
+    aL = O.zeros(Nc + (D,), T)
+    O.restrictL(aL, L)
+    CL = X.host_cells({"b": L}, N=Nc, NA=Ng)
+    for c in range(D):
+        v, M = X.restrictL(CL, c)
+        check("restrictL", aL[..., c].ravel(order="F"), v, M, T, f"restrictL {np.dtype(T).name}")
+    cx = field(Nc, T, "random", 42)
+    f = O.zeros(Ng, T)
+    O.prolongate(f, cx)
+    Cf = X.host_cells({"b": cx}, N=Ng, NA=Nc)
+    insf = np.all([(q >= 1) & (q <= n - 2) for q, n in zip(Cf.idx, Ng)], axis=0)
+    v, M = X.prolongate(Cf)
+    check("prolongate", f.ravel(order="F")[insf], v[insf], M[insf], T)
+
+
+@pytest.mark.parametrize("T", TYPES)
+def test_reductions_oracle_vs_xref(T):
+    """dot over the whole arrays: Float32 within 1 ulp of the correctly rounded exact value, Float64 within
+    4*log2(n)*eps*sum|ab|; control: one partial dropped fails."""
+    Ng = (11, 9, 7)
+    a, b = field(Ng, T, "random", 50), field(Ng, T, "random", 51)
+    got = float(O._fn("wlo_dot", T)(O._p(a), O._p(b), a.size))
+    v, M = X.dot(a, b)
+    n = a.size
+    if np.dtype(T) == np.float32:
+        assert X.ulps(got, X.round_to(v, T), T) <= 1
+    else:
+        assert abs(got - v) <= 4 * np.log2(n) * X.eps(T) * M
+    q = int(np.argmax(np.abs(a.astype(np.float64) * b).ravel(order="F")))
+    drop = v - float(a.ravel(order="F")[q]) * float(b.ravel(order="F")[q])
+    assert abs(got - drop) > 4 * np.log2(n) * X.eps(T) * M
+
+
+def test_worst_ratios_are_recorded():
+    """(prints the largest |oracle-ref|/(eps*M) seen per operator in this module: -s shows it)"""
+    print("\nworst |oracle-ref|/(eps_T*M):", {k: round(v, 3) for k, v in sorted(WORST.items())})

@@ -1,0 +1,410 @@
+"""Independent extended-precision reference of the operators (TEST INFRASTRUCTURE; numpy only).
+
+Written from the operator definitions of the reference WaterLily sources (file:line cited on every function), in GATHER
+form: each cell sums the fluxes through its own faces.  The CPU oracle (oracle/wlo_impl.h) uses the reference's scatter
+form with a Phi scratch and rounds like the reference; this module rounds nowhere: every operator is evaluated in
+np.longdouble (64-bit significand) from the T-valued inputs, and the reductions are exact (math.fsum of exact products).
+It imports neither `oracle` nor `waterlily_amd`.
+
+Every operator evaluates at an arbitrary list of cells.  A `Cells` object holds the cell indices (0-based, ghosts
+included, one int array per dimension) and a getter that returns the values of a named array at any index tuple; the
+same code therefore serves whole small host arrays and cells sampled out of full-size device fields.
+
+Each operator returns (value, M): M is the same expression tree evaluated on the absolute values of every term.  A
+product that evaluates the operator in T with any order of its roundings is within a few eps_T * M of `value`; the tests
+check |product - value| <= K * eps_T * M with K stated per operator.  Branches (`u > 0 ? ...`, the median limiter, the
+`iD == 0` test) are decided on quantities whose sign the product's rounding cannot change or are continuous in their
+inputs, so a rounding difference moves the result by a rounding amount only.
+
+Index conventions: arrays are (N1,N2[,N3]) scalars and (...,D) vectors with one ghost layer per side, extents N include
+the ghosts; 0-based index q here is the reference's 1-based q+1.
+"""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+
+LD = np.longdouble
+
+# K per operator: |T result - value| <= K * eps_T * M.  A T evaluation of each expression tree makes at most a handful of
+# roundings, each bounded by eps_T/2 of a partial sum whose magnitude M bounds; K leaves a margin of 3-4x over the
+# largest ratio measured (oracle 1.13, kernels 1.80).
+K = {"conv_diff": 8, "div": 4, "bdim_f": 4, "bdim_u": 8, "flux_out": 4, "accelerate": 1, "scale_u": 1, "diag": 4,
+     "iD": 8, "mult": 4, "residual": 8, "jacobi": 8, "alpha": 16, "pcg": 16, "restrict": 4, "restrictL": 4,
+     "prolongate": 0}
+
+
+def eps(T) -> float:
+    return float(np.finfo(np.dtype(T)).eps)
+
+
+class Cells:
+    """The cells `idx` (tuple of D int arrays) of a grid of extents N, reading arrays of extents NA (default N; the fine
+    grid for the restrictions) through get(name, index_tuple, comp) -> values.  Indices outside [0, NA) are clamped
+    before the fetch: the operators mask what such a fetch feeds."""
+
+    def __init__(self, idx, N, get, NA=None):
+        self.idx = tuple(np.asarray(a, dtype=np.int64) for a in idx)
+        self.N = tuple(int(n) for n in N)
+        self.NA = self.N if NA is None else tuple(int(n) for n in NA)
+        self.D = len(self.N)
+        self.get = get
+
+    def __len__(self):
+        return len(self.idx[0])
+
+    def at(self, name, ix, c=None) -> np.ndarray:
+        ix = tuple(np.clip(a, 0, n - 1) for a, n in zip(ix, self.NA))
+        return np.asarray(self.get(name, ix, c), dtype=LD)
+
+    def __call__(self, name, off=(), c=None) -> np.ndarray:
+        off = tuple(off) + (0,) * (self.D - len(off))
+        return self.at(name, tuple(a + o for a, o in zip(self.idx, off)), c)
+
+
+def host_cells(arrays: dict, idx=None, N=None, NA=None) -> Cells:
+    """Cells over host numpy arrays (idx=None: every cell of an array of extents N)."""
+    if idx is None:
+        idx = tuple(a.ravel(order="F") for a in np.meshgrid(*[np.arange(n) for n in N], indexing="ij"))
+
+    def get(name, ix, c):
+        a = arrays[name]
+        if a.ndim > len(ix) + 1:                                       # mu1[I,i,j]: component i + D*j
+            a = a.reshape(a.shape[:len(ix)] + (-1,), order="F")
+        return a[ix + ((c,) if c is not None else ())]
+    if N is None:
+        N = next(iter(arrays.values())).shape[:len(idx)]
+    return Cells(idx, N, get, NA)
+
+
+def dl(d, D, k=1):
+    """offset k along dimension d"""
+    return tuple(k if q == d else 0 for q in range(D))
+
+
+# ------------------------------------------------------------------------------------------------ Flow.jl
+
+def median(a, b, c):
+    """Flow.jl:25-34 (value, M) on (value, M) pairs: the result is one of the arguments, its bound the largest."""
+    (av, am), (bv, bm), (cv, cm) = a, b, c
+    gt = av > bv
+    v = np.where(gt, np.where(bv >= cv, bv, np.where(av > cv, cv, av)),
+                 np.where(bv <= cv, bv, np.where(av < cv, cv, av)))
+    return v, np.maximum(np.maximum(am, bm), cm)
+
+
+def quick(u, c, d):
+    """Flow.jl:4  quick(u,c,d) = median((5c+2d-u)/6, c, median(10c-9u, c, d))"""
+    au, ac, ad = abs(u), abs(c), abs(d)
+    a1 = ((5 * c + 2 * d - u) / 6, (5 * ac + 2 * ad + au) / 6)
+    a2 = median((10 * c - 9 * u, 10 * ac + 9 * au), (c, ac), (d, ad))
+    return median(a1, (c, ac), a2)
+
+
+def _face_flux(C: Cells, j: int, c: int, F, nu, kind: str):
+    """Flux of component c through the j-face at cell index F (Flow.jl:45 / :54 / :55 / :58-59 before the sign of the
+    upper boundary): phi-weighted upwind term minus nu * d(u_c)/dx_j.  kind: 'u' (ϕu, :6), 'L' (ϕuL, :8), 'R' (ϕuR, :9),
+    'P' (ϕuP, :7 with the far-upwind point at j-index N_j-2)."""
+    D = C.D
+    sh = lambda k: tuple(a + o for a, o in zip(F, dl(j, D, k)))
+    uf_a, uf_b = C.at("u", F, j), C.at("u", tuple(a - o for a, o in zip(F, dl(c, D))), j)
+    uf, Muf = (uf_a + uf_b) * LD(0.5), (abs(uf_a) + abs(uf_b)) * LD(0.5)   # ϕ(i,CI(I,j),u)  Flow.jl:3
+    b, cc, d = C.at("u", sh(-1), c), C.at("u", F, c), C.at("u", sh(1), c)
+    if kind == "P":
+        Ip = tuple(np.full_like(a, C.N[j] - 3) if q == j else a for q, a in enumerate(F))
+        a = C.at("u", Ip, c)
+    else:
+        a = C.at("u", sh(-2), c)
+    qp, qn = quick(a, b, cc), quick(d, cc, b)
+    ph = ((cc + b) * LD(0.5), (abs(cc) + abs(b)) * LD(0.5))              # ϕ(j,I,u_c)
+    pos = uf > 0
+    if kind == "L":
+        lam = (np.where(pos, ph[0], qn[0]), np.where(pos, ph[1], qn[1]))
+    elif kind == "R":
+        neg = uf < 0
+        lam = (np.where(neg, ph[0], qp[0]), np.where(neg, ph[1], qp[1]))
+    else:
+        lam = (np.where(pos, qp[0], qn[0]), np.where(pos, qp[1], qn[1]))
+    nu = LD(nu)
+    v = uf * lam[0] - nu * (cc - b)
+    M = Muf * lam[1] + abs(nu) * (abs(cc) + abs(b))
+    return v, M
+
+
+def conv_diff(C: Cells, c: int, nu, perdir=()):
+    """Flow.jl:36-60 conv_diff!, component c of r at the cells of C, gather form: r[I,c] = sum_j (flux through the lower
+    j-face of I) - (flux through its upper j-face).  Which faces exist follows the loop ranges: lower boundary faces on
+    j-index 2 (slice(N,2,j,2), :54/:58), interior faces 3:N-1 (inside_u(N,j), :45-47), upper boundary faces on N (:55/:60),
+    every other index in 2:N -- so r is 0 on the cells with a 1-based index 1 and gets no j-fluxes where its j-index is N."""
+    D = C.D
+    v = np.zeros(len(C), LD)
+    M = np.zeros(len(C), LD)
+    alive = np.all([a >= 1 for a in C.idx], axis=0)
+    for j in range(D):
+        m, N = C.idx[j], C.N[j]
+        per = j in perdir
+        has = alive & (m <= N - 2)                          # cell's lower face 1-based m+1 in 2:N-1, upper m+2 in 3:N
+        lo_kind = "P" if per else "L"
+        for sgn, F, f in ((1, C.idx, m), (-1, tuple(a + o for a, o in zip(C.idx, dl(j, D))), m + 1)):
+            fv = np.zeros(len(C), LD)
+            fM = np.zeros(len(C), LD)
+            for kind, sel in (("u", (f >= 2) & (f <= N - 2)), (lo_kind, f == 1),
+                              ("R" if not per else "P", f == N - 1)):
+                sel = sel & has
+                if not np.any(sel):
+                    continue
+                FF = F
+                if per and kind == "P" and np.any(f == N - 1):
+                    # :60  r[I-δ(j),i] -= Φ[CIj(j,I,2)]: the top face repeats the flux of the bottom face
+                    FF = tuple(np.where(f == N - 1, 1, a) if q == j else a for q, a in enumerate(F))
+                fx = _face_flux(C, j, c, FF, nu, kind)
+                fv = np.where(sel, fx[0], fv)
+                fM = np.where(sel, fx[1], fM)
+            v += sgn * fv
+            M += fM
+    return v, M
+
+
+def div(C: Cells):
+    """Flow.jl:11-17 with ∂ of Flow.jl:2: sum_i u[I+δi,i] - u[I,i]"""
+    v = np.zeros(len(C), LD)
+    M = np.zeros(len(C), LD)
+    for i in range(C.D):
+        a, b = C("u", dl(i, C.D), i), C("u", (), i)
+        v += a - b
+        M += abs(a) + abs(b)
+    return v, M
+
+
+def flux_out(C: Cells):
+    """Flow.jl:176-182 (the σ that CFL, :172-175, maximises)"""
+    v = np.zeros(len(C), LD)
+    for i in range(C.D):
+        v += np.maximum(LD(0), C("u", dl(i, C.D), i)) + np.maximum(LD(0), -C("u", (), i))
+    return v, v.copy()
+
+
+def bdim_f(C: Cells, c: int, dt, off=()):
+    """Flow.jl:133  f = u⁰ + dt*f - V (every cell) at C's cells shifted by `off`"""
+    u0, f, V = C("u0", off, c), C("f", off, c), C("V", off, c)
+    dt = LD(dt)
+    return u0 + dt * f - V, abs(u0) + abs(dt) * abs(f) + abs(V)
+
+
+def bdim_u(C: Cells, c: int, dt):
+    """Flow.jl:134 with μddn of Flow.jl:18-24: u += 0.5*sum_j μ₁[I,c,j]*(f[I+δj]-f[I-δj]) + V + μ₀*f, f from :133.
+    Inside cells only (inside_u(size(p)))."""
+    D = C.D
+    s = np.zeros(len(C), LD)
+    Ms = np.zeros(len(C), LD)
+    for j in range(D):
+        m1 = C("mu1", (), c + D * j)
+        fp, Mp = bdim_f(C, c, dt, dl(j, D))
+        fm, Mm = bdim_f(C, c, dt, dl(j, D, -1))
+        s += m1 * (fp - fm)
+        Ms += abs(m1) * (Mp + Mm)
+    f0, M0 = bdim_f(C, c, dt)
+    u, V, mu0 = C("u", (), c), C("V", (), c), C("mu0", (), c)
+    return u + LD(0.5) * s + V + mu0 * f0, abs(u) + LD(0.5) * Ms + abs(V) + abs(mu0) * M0
+
+
+def accelerate(C: Cells, c: int, g):
+    """Flow.jl:68-70  r[..,i] .+= g_i (every cell)"""
+    r = C("r", (), c)
+    return r + LD(g), abs(r) + abs(LD(g))
+
+
+def scale_u(C: Cells, c: int, s):
+    """Flow.jl:170  u *= scale over inside cells"""
+    u = C("u", (), c)
+    return u * LD(s), abs(u * LD(s))
+
+
+# ------------------------------------------------------------------------------------------------ Poisson.jl
+
+def diag(C: Cells):
+    """Poisson.jl:48-54  D[I] = -sum_i (L[I,i] + L[I+δi,i])"""
+    v = np.zeros(len(C), LD)
+    M = np.zeros(len(C), LD)
+    for i in range(C.D):
+        a, b = C("L", (), i), C("L", dl(i, C.D), i)
+        v -= a + b
+        M += abs(a) + abs(b)
+    return v, M
+
+
+def inv_diag(Dv, DM, T):
+    """Poisson.jl:44  iD = abs2(D) < 2eps(T) ? 0 : inv(D).  (value, M) with M = |1/D| * (1 + DM/|D|): the bound of 1/D under
+    a relative perturbation DM/|D| of D.  Cells whose exact D sits within the rounding of the threshold have M = inf
+    (either answer is right) -- the tests keep away from them."""
+    e = LD(eps(T))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        zero = Dv * Dv < 2 * e
+        v = np.where(zero, LD(0), 1 / np.where(zero, LD(1), Dv))
+        near = abs(Dv * Dv - 2 * e) <= 8 * e * (DM * DM + abs(Dv * Dv))
+        M = np.where(zero, LD(0), abs(v) * (1 + DM / abs(np.where(zero, LD(1), Dv))))
+    return v, np.where(near, LD(np.inf), M)
+
+
+def mult(C: Cells, x="x"):
+    """Poisson.jl:69-75  z[I] = x[I]*D[I] + sum_i x[I-δi]*L[I,i] + x[I+δi]*L[I+δi,i]  (D as stored)"""
+    D = C.D
+    xv, Dv = C(x), C("D")
+    v, M = xv * Dv, abs(xv * Dv)
+    for i in range(D):
+        a = C(x, dl(i, D, -1)) * C("L", (), i)
+        b = C(x, dl(i, D)) * C("L", dl(i, D), i)
+        v += a + b
+        M += abs(a) + abs(b)
+    return v, M
+
+
+def residual_local(C: Cells):
+    """Poisson.jl:93  r = iD == 0 ? 0 : z - A x   (before the mean shift)"""
+    Av, AM = mult(C)
+    z, iD = C("z"), C("iD")
+    return np.where(iD == 0, LD(0), z - Av), np.where(iD == 0, LD(0), abs(z) + AM)
+
+
+def jacobi_increment(C: Cells):
+    """Poisson.jl:110-113 + :99-103, one sweep: ϵ = r*iD; r -= A ϵ; x += ϵ.  Returns ((eps, M), (r, M), (x, M)).
+    The neighbours' ϵ are r*iD at the neighbours."""
+    D = C.D
+    e, eM = C("r") * C("iD"), abs(C("r") * C("iD"))
+    Ae, AeM = e * C("D"), eM * abs(C("D"))
+    for i in range(D):
+        for k, Lo in ((-1, ()), (1, dl(i, D))):
+            en = C("r", dl(i, D, k)) * C("iD", dl(i, D, k))
+            L = C("L", Lo, i)
+            Ae += en * L
+            AeM += abs(en) * abs(L)
+    r, x = C("r"), C("x")
+    return (e, eM), (r - Ae, abs(r) + AeM), (x + e, abs(x) + eM)
+
+
+# ------------------------------------------------------------------------------------------------ MultiLevelPoisson.jl
+
+def restrict(C: Cells, name="b"):
+    """MultiLevelPoisson.jl:3-9,33  a[I] = sum of b over up(I) = the 2^D fine cells 2I-2:2I-1 (1-based); C: COARSE cells,
+    the getter reads the fine array"""
+    v = np.zeros(len(C), LD)
+    M = np.zeros(len(C), LD)
+    D = C.D
+    for corner in np.ndindex(*(2,) * D):
+        ix = tuple(2 * a - 1 + o for a, o in zip(C.idx, corner))
+        b = C.at(name, ix)
+        v += b
+        M += abs(b)
+    return v, M
+
+
+def restrictL(C: Cells, c: int, name="b"):
+    """MultiLevelPoisson.jl:10-16,26-32 restrictL! of component c at COARSE cells (non-periodic): 0.5 * the 2^(D-1) fine
+    faces up(I,c) on 2:n-1, then BC!(a, 0) (util.jl:192-210): planes 1, 2 and N of the normal direction hold 0, every
+    other ghost cell the value of the nearest inside cell."""
+    D = C.D
+    cl = tuple(np.clip(a, 1, n - 2) for a, n in zip(C.idx, C.N))        # tangential zero-Neumann ghosts
+    v = np.zeros(len(C), LD)
+    M = np.zeros(len(C), LD)
+    for corner in np.ndindex(*(2,) * D):
+        if corner[c]:
+            continue
+        ix = tuple(2 * a - 1 + o for a, o in zip(cl, corner))
+        b = C.at(name, ix, c)
+        v += b
+        M += abs(b)
+    m = C.idx[c]
+    wall = (m <= 1) | (m == C.N[c] - 1)
+    return np.where(wall, LD(0), LD(0.5) * v), np.where(wall, LD(0), LD(0.5) * M)
+
+
+def prolongate(C: Cells, name="b"):
+    """MultiLevelPoisson.jl:2,34  a[I] = b[down(I)], down(I) = (I+2)÷2 (1-based): a copy, exact.  C: FINE inside cells."""
+    v = C.at(name, tuple((a + 1) // 2 for a in C.idx))
+    return v, abs(v)
+
+
+def pcg1_ref(L, D, iD, r):
+    """One pcg! iteration (Poisson.jl:123-135, it=1) from x = 0 on whole host arrays: (alpha, M_alpha, eps, z, x1, r1)
+    as (value, M) pairs; rho and z.eps are exact sums over the whole arrays."""
+    Ng = r.shape
+    C = host_cells({"r": r, "iD": iD}, N=Ng)
+    e = (C("r") * C("iD")).reshape(Ng, order="F")
+    eM = abs(e)
+    Ce = host_cells({"L": L, "D": D, "e": e.astype(np.float64)}, N=Ng)
+    ins = np.all([(q >= 1) & (q <= n - 2) for q, n in zip(Ce.idx, Ng)], axis=0)
+    zv, zM = mult(Ce, "e")
+    zv, zM = np.where(ins, zv, 0), np.where(ins, zM, 0)
+    rf = r.ravel(order="F").astype(LD)
+    ef = e.ravel(order="F")
+    rho = np.sum(rf * ef)
+    ze = np.sum(zv * ef)
+    Mrho = 2 * np.sum(abs(rf) * eM.ravel(order="F"))
+    Mze = 2 * np.sum(zM * eM.ravel(order="F"))
+    alpha = rho / ze
+    Ma = abs(alpha) * (Mrho / abs(rho) + Mze / abs(ze))
+    x1 = (alpha * ef, abs(alpha) * eM.ravel(order="F") + Ma * abs(ef))
+    r1 = (rf - alpha * zv, abs(rf) + abs(alpha) * zM + Ma * abs(zv))
+    return (alpha, Ma), (ef, eM.ravel(order="F")), (zv, zM), x1, r1, ins
+
+
+# ------------------------------------------------------------------------------------------------ reductions
+
+def _two_prod(a: np.ndarray, b: np.ndarray):
+    """exact a*b = p + e for float64 a, b (Dekker / Veltkamp split)"""
+    a = np.asarray(a, np.float64)
+    b = np.asarray(b, np.float64)
+    p = a * b
+    sp = 134217729.0                                                   # 2^27 + 1
+    with np.errstate(over="ignore", invalid="ignore"):
+        ta, tb = sp * a, sp * b
+        ah = ta - (ta - a)
+        bh = tb - (tb - b)
+    al, bl = a - ah, b - bh
+    e = ((ah * bh - p) + ah * bl + al * bh) + al * bl
+    return p, e
+
+
+def dot(a: np.ndarray, b: np.ndarray):
+    """LinearAlgebra.dot over the whole arrays, ghost cells included (Poisson.jl:126,131,137,146): the exact sum, correctly
+    rounded to float64, and M = sum |a_i b_i| (also correctly rounded)."""
+    p, e = _two_prod(np.ravel(a), np.ravel(b))
+    return math.fsum(np.concatenate([p, e])), math.fsum(np.abs(np.concatenate([p, e])))
+
+
+def L2_inside(a: np.ndarray):
+    """util.jl:68  sum(abs2, a[inside])"""
+    a = a[tuple(slice(1, n - 1) for n in a.shape)]
+    return dot(a, a)
+
+
+def Linf(a: np.ndarray) -> float:
+    """Poisson.jl:147  maximum(abs, p.r) over the whole array: exact"""
+    return float(np.max(np.abs(np.asarray(a, np.float64))))
+
+
+def round_to(x: float, T) -> float:
+    """x (a float64 holding the correctly rounded exact value) rounded once more to T"""
+    return float(np.dtype(T).type(x))
+
+
+def ulps(x: float, ref: float, T) -> float:
+    """|x - ref| in units of the T spacing at ref"""
+    sp = float(np.spacing(np.abs(np.dtype(T).type(ref))))
+    return abs(float(x) - float(ref)) / sp
+
+
+def ratio(got, v, M, T) -> np.ndarray:
+    """|got - v| / (eps_T * M) per cell; cells with M == 0 must be exact (ratio 0 or inf)"""
+    got = np.asarray(got, dtype=LD)
+    d = abs(got - v)
+    e = LD(eps(T))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        r = np.where(M > 0, d / (e * M), np.where(d == 0, LD(0), LD(np.inf)))
+    return r.astype(np.float64)
+
+
+def worst(got, v, M, T) -> float:
+    r = ratio(got, v, M, T)
+    return float(np.max(r)) if r.size else 0.0

@@ -1,0 +1,108 @@
+"""Adversarial inputs shared by the xref checks (test_xref_cpu.py against the oracle, test_xref_gpu.py against the kernels)."""
+import numpy as np
+
+KINDS = ["random", "ties", "step", "scaled-up", "scaled-down"]
+
+
+def field(shape, T, kind, seed, lo=-1.0, hi=1.0, seam=64):
+    """random: uniform in [lo,hi); ties: values in {-1,-1/2,0,1/2,1} (exact median ties, u == 0 faces); step: two levels
+    with fronts along x at the x-tile seams (every `seam` cells from 1) and along y/z at index 4; scaled-*: random times
+    2^±20 (Float32) / 2^±60 (Float64)."""
+    rng = np.random.default_rng(seed)
+    T = np.dtype(T)
+    if kind == "ties":
+        a = rng.integers(-2, 3, size=shape) * 0.5
+    elif kind == "step":
+        ix = np.indices(shape[:3] if len(shape) >= 3 else shape)
+        x = ix[0]
+        s = ((x - 1) // seam) % 2 + (ix[1] >= 4)
+        if len(ix) > 2:
+            s = s + (ix[2] >= 4)
+        s = s.astype(np.float64)
+        a = np.broadcast_to(s.reshape(s.shape + (1,) * (len(shape) - s.ndim)), shape) - 1.0 + 0.01 * rng.random(shape)
+    else:
+        a = lo + (hi - lo) * rng.random(shape)
+        if kind == "scaled-up":
+            a = a * 2.0 ** (20 if T == np.float32 else 60)
+        elif kind == "scaled-down":
+            a = a * 2.0 ** (-20 if T == np.float32 else -60)
+    return np.asfortranarray(np.asarray(a, dtype=T))
+
+
+def coefficients(Ng, T, seed, kind="body", edge=None, seam=64):
+    """Face coefficients L (Ng + (D,)) in [0.2, 1] with a body: a block of L = 0 cells (solid, iD = 0 there), and with
+    kind="row" a unit field where one x-row differs in a single coefficient: edge in {"f1","f2","seam","n-2","n-1","y","z"}
+    picks the row's first and second free x face (0-based 2, 3), the face at x = seam + 1, the last two free faces (0-based
+    n0-3, n0-2), or L_y[j+1] / L_z[k+1]."""
+    D = len(Ng)
+    rng = np.random.default_rng(seed)
+    if kind == "row":
+        L = np.ones(Ng + (D,), T, order="F")
+        j, k = min(2, Ng[1] - 2), (min(2, Ng[2] - 2) if D == 3 else None)
+        row = (slice(None), j) + ((k,) if D == 3 else ())
+        n0 = Ng[0]
+        # 0-based index of the x face: BC! keeps 0 on faces 0, 1 and n0-1, so the row's first free face is 2
+        i = {"f1": 2, "f2": 3, "seam": min(seam + 1, n0 - 2), "n-2": n0 - 3, "n-1": n0 - 2}.get(edge)
+        if i is not None:
+            L[(i,) + row[1:] + (0,)] = T(0.75)
+        elif edge == "y":
+            L[(min(3, n0 - 2), j + 1) + ((k,) if D == 3 else ()) + (1,)] = T(0.75)
+        elif edge == "z" and D == 3:
+            L[(min(3, n0 - 2), j, k + 1, 2)] = T(0.75)
+        keep = L.copy()
+    else:
+        L = np.asfortranarray((0.2 + 0.8 * rng.random(Ng + (D,))).astype(T))
+        blk = tuple(slice(max(1, n // 3), max(2, n // 3 + 2)) for n in Ng)
+        L[blk] = 0                                         # a solid block: its cells have D = 0, iD = 0
+    # BC!(L, 0): zero normal coefficient on planes 1, 2 and N, zero-Neumann tangential ghosts (util.jl:192-210)
+    for c in range(D):
+        for j in range(D):
+            sl = lambda q: tuple(q if d == j else slice(None) for d in range(D)) + (c,)
+            if c == j:
+                for q in (0, 1, Ng[j] - 1):
+                    L[sl(q)] = 0
+            else:
+                L[sl(0)] = L[sl(1)]
+                L[sl(Ng[j] - 1)] = L[sl(Ng[j] - 2)]
+    if kind == "row" and edge is not None:
+        assert np.any(L == T(0.75)) and np.any(keep == T(0.75)), "the odd coefficient must survive BC!"
+    return L
+
+
+
+def device_cells(tensors: dict, idx, N, NA=None):
+    """xref.Cells over device fields (any strides, padded or dense): the values are gathered on the device by flat
+    offset -- int64 throughout, C4 vector fields span more than 2^32 elements -- and copied to the host."""
+    import torch
+    import xref as X
+    base = {}
+    for k, t in tensors.items():
+        span = 1 + sum((n - 1) * s for n, s in zip(t.shape, t.stride()))
+        base[k] = (torch.as_strided(t, (span,), (1,), t.storage_offset()), t.stride())
+    D = len(N)
+
+    def get(name, ix, c):
+        b, st = base[name]
+        off = sum(torch.as_tensor(a, device=b.device) * st[d] for d, a in enumerate(ix))
+        if c is not None:
+            off = off + c * st[D]
+        return b[off].cpu().numpy()
+    return X.Cells(idx, N, get, NA)
+
+
+def samples(Ng, nrand, seed, row_step=None):
+    """Inside cells of a grid of extents Ng (ghosts included) to compare at: `nrand` random cells; the x rows of the planes
+    k = 1, 2, mid, N-1, N (1-based inside planes, every `row_step`-th row: all rows when None); every inside plane of four
+    (i, j) columns -- every z-chunk seam -- among them the last row's last cell, the highest addresses of a field."""
+    rng = np.random.default_rng(seed)
+    n0, n1, n2 = Ng
+    out = [tuple(rng.integers(1, n - 1, size=nrand) for n in Ng)]
+    step = row_step or 1
+    for k in sorted({1, 2, n2 // 2, n2 - 3, n2 - 2}):
+        i, j = np.meshgrid(np.arange(1, n0 - 1), np.arange(1, n1 - 1, step), indexing="ij")
+        j = np.where(j == j.max(), n1 - 2, j)                     # the last row always in
+        out.append((i.ravel(), j.ravel(), np.full(i.size, k)))
+    k = np.arange(1, n2 - 1)
+    for i, j in ((1, 1), (n0 // 2, n1 // 3), (n0 - 2, 1), (n0 - 2, n1 - 2)):
+        out.append((np.full(k.size, i), np.full(k.size, j), k))
+    return tuple(np.concatenate([o[d] for o in out]).astype(np.int64) for d in range(3))

@@ -365,7 +365,7 @@ template <class T, int D> static int mg_Linf(wl_mg *m, int l) {
     LevelT<T> p = lvl<T>(m, l);
     const T *r = p.r;
     return op_reduce<T, D>(p.g, WL_K_DOT, RED_MAX, 0.0, [=] __device__(long I) { const double v = (double)r[I]; return v < 0 ? -v : v; },
-                           m->sc.partials, m->sc.st, 1);
+                           m->sc.partials, m->sc.st, 1, true);   // the whole array, ghost cells included
 }
 // one row of the reference's solver log: `@log ", $n, $(L∞(p)), $r₂\n"` (Poisson.jl:164,167; MultiLevelPoisson.jl:90,94)
 template <class T, int D> static int mg_log_row(wl_mg *m, int n, bool have_r2) {
