@@ -306,6 +306,20 @@ enum { WL_M_KE = 0, WL_M_CURL = 1, WL_M_OMAG = 2, WL_M_OTHETA = 3, WL_M_LAMBDA2 
 int wl_metric(wl_dtype t, const wl_grid *g, int kind, void *out, const void *u, int ipar, const double par[3],
               const double par2[3]);
 
+/* ------------------------------------------------------------------ time-averaged statistics (MeanFlow, waterlily_amd/stats.py)
+ * One update of running means of u and p, and optionally of the velocity covariance (Reynolds stress) and the pressure
+ * variance, over EVERY element of the local arrays (ghost cells and z-slab halo planes included; row padding untouched):
+ *   d_c = u_c - U_c;  U_c <- U_c + eps d_c;  UU_ij <- (1-eps)(UU_ij + eps d_i d_j);  the same for P, pp with d = p - P
+ * in double arithmetic, each store rounded once to t_acc.  eps = dt / (t - t0) in (0, 1], computed by the host in Float64.
+ * first != 0 (the first update of an averaging window, eps == 1): U = u, P = p, UU = pp = 0, and the accumulators are not
+ * read.  u, p: the flow's fields on grid g (t_flow); U (D components), P, UU (D(D+1)/2 components in ParaView's
+ * symmetric-tensor order: 3-D xx yy zz xy yz xz, 2-D xx yy xy) and pp on grid ga (t_acc: same extents and slab as g, the
+ * strides may differ).  UU / pp may be NULL (not collected).  The products pair u[I,i] u[I,j] at the same index I (face
+ * values of different faces).  t_flow = WL_F64 with t_acc = WL_F32 is refused.  Asynchronous.  WaterLily v1.3 has no
+ * MeanFlow to override: the entry point is there for a later binding. */
+int wl_meanflow_update(wl_dtype t_flow, wl_dtype t_acc, const wl_grid *g, const void *u, const void *p, const wl_grid *ga, void *U,
+                       void *P, void *UU, void *pp, double eps, int first);
+
 /* ------------------------------------------------------------------ snapshots (VTK write / restart, ext/WaterLilyWriteVTKExt.jl:57-66,
  * ext/WaterLilyReadVTKExt.jl:28-45).  The reference copies whole fields to the host (`a.flow.u |> Array`) and permutes the vector
  * components to the front there (components_first, :79).  Here the field's LOCAL planes klo..khi are packed on the device into

@@ -152,6 +152,7 @@ def lib() -> C.CDLL:
         "wl_pforce": (i, [i, gp, vp, vp, vp, i64, dp]),
         "wl_vforce": (i, [i, gp, vp, vp, vp, i64, d, dp]),
         "wl_pmoment": (i, [i, gp, vp, vp, vp, i64, dp, dp]),
+        "wl_meanflow_update": (i, [i, i, gp, vp, vp, gp, vp, vp, vp, vp, d, i]),
         "wl_snapshot_pack": (i, [i, gp, vp, i, i, i, i, vp]),
         "wl_snapshot_unpack": (i, [i, gp, vp, i, i, i, i, vp]),
         "wl_set_option": (i, [i, i]),

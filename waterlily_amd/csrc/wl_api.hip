@@ -12,6 +12,7 @@
 #include "wl_ops.h"
 #include "wl_coarse.h"
 #include "wl_measure.h"
+#include "wl_stats.h"
 
 namespace wl {
 
@@ -1400,6 +1401,33 @@ int wl_metric(wl_dtype t, const wl_grid *g, int kind, void *out, const void *u, 
     if (kind < 0 || kind > WL_M_LAMBDA2 || (kind >= WL_M_OMAG && g->D != 3) || (kind == WL_M_CURL && (ipar < 0 || ipar > 2)))
         return fail(WL_E_ARG, "wl_metric: bad kind/component for this dimension", __FILE__, __LINE__);
     WL_DISPATCH(t, g->D, (op_metric<T, DD>(gg, kind, (T *)out, (const T *)u, ipar, par, par2)));
+}
+int wl_meanflow_update(wl_dtype t_flow, wl_dtype t_acc, const wl_grid *g, const void *u, const void *p, const wl_grid *ga, void *U,
+                       void *P, void *UU, void *pp, double eps, int first) {
+    WL_TRY(check_grid(g));
+    WL_TRY(check_grid(ga));
+    if ((t_flow != WL_F32 && t_flow != WL_F64) || (t_acc != WL_F32 && t_acc != WL_F64))
+        return fail(WL_E_ARG, "wl_meanflow_update: unknown dtype", __FILE__, __LINE__);
+    if (t_flow == WL_F64 && t_acc == WL_F32)
+        return fail(WL_E_ARG, "wl_meanflow_update: Float32 accumulators on a Float64 flow", __FILE__, __LINE__);
+    if (!u || !p || !U || !P) return fail(WL_E_ARG, "wl_meanflow_update: null u, p, U or P", __FILE__, __LINE__);
+    bool same = ga->D == g->D && ga->nzg == g->nzg;
+    for (int d = 0; d < 3; ++d) same = same && ga->n[d] == g->n[d];
+    if (same && g->D == 3 && g->nzg > 0)
+        same = ga->kz0 == g->kz0 && ga->own_lo == g->own_lo && ga->own_hi == g->own_hi && ga->zring == g->zring;
+    if (!same) return fail(WL_E_ARG, "wl_meanflow_update: the accumulators' grid must have the flow grid's extents and slab", __FILE__, __LINE__);
+    if (!(eps > 0.0 && eps <= 1.0)) return fail(WL_E_ARG, "wl_meanflow_update: eps must lie in (0, 1]", __FILE__, __LINE__);
+    const G gf = mkG(g), gacc = mkG(ga);
+    if (t_flow == WL_F32 && t_acc == WL_F32) {
+        if (g->D == 2) return op_meanflow<float, float, 2>(gf, gacc, (const float *)u, (const float *)p, (float *)U, (float *)P, (float *)UU, (float *)pp, eps, first);
+        return op_meanflow<float, float, 3>(gf, gacc, (const float *)u, (const float *)p, (float *)U, (float *)P, (float *)UU, (float *)pp, eps, first);
+    }
+    if (t_flow == WL_F32) {
+        if (g->D == 2) return op_meanflow<float, double, 2>(gf, gacc, (const float *)u, (const float *)p, (double *)U, (double *)P, (double *)UU, (double *)pp, eps, first);
+        return op_meanflow<float, double, 3>(gf, gacc, (const float *)u, (const float *)p, (double *)U, (double *)P, (double *)UU, (double *)pp, eps, first);
+    }
+    if (g->D == 2) return op_meanflow<double, double, 2>(gf, gacc, (const double *)u, (const double *)p, (double *)U, (double *)P, (double *)UU, (double *)pp, eps, first);
+    return op_meanflow<double, double, 3>(gf, gacc, (const double *)u, (const double *)p, (double *)U, (double *)P, (double *)UU, (double *)pp, eps, first);
 }
 int wl_pforce(wl_dtype t, const wl_grid *g, const void *p, const int64_t *idx, const double *nds, int64_t nband,
               double out[3]) {
