@@ -7,7 +7,7 @@ import pytest
 
 import xref as X
 from oracle import wl_oracle as O
-from xref_inputs import KINDS, coefficients, field
+from xref_inputs import KINDS, coefficients, field, periodic_subsets, step_fields
 
 TYPES = [np.float32, np.float64]
 K = X.K
@@ -215,6 +215,123 @@ def test_multilevel_transfers_oracle_vs_xref(T, Ng):
     insf = np.all([(q >= 1) & (q <= n - 2) for q, n in zip(Cf.idx, Ng)], axis=0)
     v, M = X.prolongate(Cf)
     check("prolongate", f.ravel(order="F")[insf], v[insf], M[insf], T)
+
+
+@pytest.mark.parametrize("T", TYPES)
+@pytest.mark.parametrize("Ng,perdir", [(Ng, p) for Ng in [(10, 10), (10, 8, 6)] for p in periodic_subsets(len(Ng))])
+def test_restrictL_periodic_oracle_vs_xref(T, Ng, perdir):
+    """restrictL! with periodic directions (K = 4): BC!(a, 0, false, perdir) leaves periodic copies in the ghost planes
+    of those directions and the normal component's plane 2 un-zeroed, applied in BC!'s (i, j) loop order; every cell of
+    the coarse array, ghost cells included.  Control: the wall-case reference must fail."""
+    D = len(Ng)
+    Nc = tuple(1 + n // 2 for n in Ng)
+    L = field(Ng + (D,), T, "random", 43, 0.2, 1.0)            # no zeroed planes: plane 2's normal face is not 0
+    aL = O.zeros(Nc + (D,), T)
+    O.restrictL(aL, L, perdir=perdir)
+    CL = X.host_cells({"b": L}, N=Nc, NA=Ng)
+    for c in range(D):
+        got = aL[..., c].ravel(order="F")
+        v, M = X.restrictL(CL, c, perdir=perdir)
+        check("restrictL", got, v, M, T, f"restrictL periodic {np.dtype(T).name}")
+        assert fails("restrictL", got, *X.restrictL(CL, c), T)      # (ghost copies, and plane 2 of c in perdir)
+
+
+def _oracle_twin_step(a, b, T):
+    """mom_step! of the oracle replayed from its operators (wlo_impl.h: wlo_mom_step's sequence): returns u', the
+    predictor's projected velocity, which the oracle's own step overwrites"""
+    D = a.D
+    U = O.BCTuple(a.U, a.dt, D)
+    gp, gc = O.accel_tuple(a.g, a.U, a.dt[:-1], D), O.accel_tuple(a.g, a.U, a.dt, D)
+    ins = tuple(slice(1, n - 1) for n in a.N)
+    a.u0[...] = a.u
+    a.u[ins] *= T(0)
+    O.conv_diff(a.f, a.u0, a.sigma, nu=a.nu, perdir=a.perdir)
+    if gp is not None:
+        O.accelerate(a.f, gp)
+    O.BDIM(a)
+    O.BC(a.u, U, False, a.perdir)
+    O.project(a, b)
+    O.BC(a.u, U, False, a.perdir)
+    up = a.u.copy(order="F")
+    O.conv_diff(a.f, a.u, a.sigma, nu=a.nu, perdir=a.perdir)
+    if gc is not None:
+        O.accelerate(a.f, gc)
+    O.BDIM(a)
+    a.u[ins] *= T(0.5)
+    O.BC(a.u, U, False, a.perdir)
+    O.project(a, b, 0.5)
+    O.BC(a.u, U, False, a.perdir)
+    a.dt.append(O.CFL(a))
+    return up, gc
+
+
+@pytest.mark.parametrize("T", TYPES)
+@pytest.mark.parametrize("dims,perdir", [((20, 12, 8), ()), ((24, 16), ()), ((24, 16), (0,))])
+def test_mom_step_corrector_f_oracle_vs_xref(T, dims, perdir):
+    """After one mom_step! f holds the corrector's BDIM! value u_start + dt*(conv_diff(u') + g_corr) - V (Flow.jl:164-166,
+    :133), K = 12 (xref.mom_f).  u' is taken from the oracle's own operators replayed in mom_step!'s order, held
+    bit-identical to the oracle's step first.  Inputs: a non-uniform u, a body block with V != 0, a time-dependent body
+    force.  Controls: dt off by 64K eps, the samples shifted one plane, u_start replaced by u' must fail."""
+    D = len(dims)
+    Ng = tuple(n + 2 for n in dims)
+    tn = np.dtype(T).name
+    g = lambda i, t: 0.05 * (i + 1) * (1 + t)
+    h = step_fields(Ng, T, 70, tuple(slice(2, max(3, n // 2)) for n in Ng))
+    U = (1.0,) + (0.0,) * (D - 1)
+    runs = []
+    for _ in range(2):
+        a = O.Flow(dims, U, T=T, nu=0.05, g=g, perdir=perdir)
+        for k in ("u", "mu0", "mu1", "V"):
+            getattr(a, k)[...] = h[k]
+        O.BC(a.u, U, False, perdir)
+        O.BC(a.mu0, (0.0,) * D, False, perdir)
+        O.BC(a.V, (0.0,) * D, False, perdir)
+        runs.append((a, O.MultiLevelPoisson(a.p, a.mu0, a.sigma, perdir=perdir)))
+    (a, b), (a2, b2) = runs
+    us = a.u.copy(order="F")
+    dt = a.dt[-1]
+    O.mom_step(a, b)
+    up, gc = _oracle_twin_step(a2, b2, T)
+    for k in ("u", "f", "p"):
+        assert np.array_equal(getattr(a, k), getattr(a2, k)), k
+    assert b.n == b2.n and a.dt == a2.dt
+    assert not np.array_equal(up, us)
+    C = X.host_cells({"u": up, "us": us, "V": a.V}, N=Ng)
+    ins = np.all([(q >= 1) & (q <= n - 2) for q, n in zip(C.idx, Ng)], axis=0)
+    for c in range(D):
+        got = a.f[..., c].ravel(order="F")[ins]
+        v, M = X.mom_f(C, c, a.nu, dt, gc[c], perdir)
+        check("mom_f", got, v[ins], M[ins], T, f"mom_step f {tn}")
+        assert fails("mom_f", got, *[q[ins] for q in X.mom_f(C, c, a.nu, dt * (1 + 64 * K["mom_f"] * X.eps(T)), gc[c], perdir)], T)
+        C0 = X.host_cells({"u": up, "us": up, "V": a.V}, N=Ng)
+        assert fails("mom_f", got, *[q[ins] for q in X.mom_f(C0, c, a.nu, dt, gc[c], perdir)], T)
+        sh = X.host_cells({"u": up, "us": us, "V": a.V}, idx=tuple(q + (d == D - 1) for d, q in enumerate(C.idx)), N=Ng)
+        m = ins & (C.idx[D - 1] < Ng[D - 1] - 2)
+        vs, Ms = X.mom_f(sh, c, a.nu, dt, gc[c], perdir)
+        assert fails("mom_f", a.f[..., c].ravel(order="F")[m], vs[m], Ms[m], T)
+
+
+@pytest.mark.parametrize("T", TYPES)
+@pytest.mark.parametrize("dims", [(32, 32, 32), (64, 32), (512, 8, 8)])
+def test_vcycle_coarse_invariant_oracle_vs_xref(T, dims):
+    """After Vcycle!(ml, 0) level 1 satisfies r + A x = rhs, rhs = restrict! of level 0's Jacobi! residual (xref.vcycle_rhs,
+    xref.coarse_defect; K = coarse_inv) -- the invariant the GPU file holds the coarse tail to; control: one face of level
+    1's L off by 25 % in the reference fails."""
+    Ng = tuple(n + 2 for n in dims)
+    L = coefficients(Ng, T, 5)
+    z = field(Ng, T, "random", 6)
+    ins = tuple(slice(1, n - 1) for n in Ng)
+    z[ins] -= z[ins].mean().astype(T)
+    po = O.MultiLevelPoisson(np.zeros(Ng, T, order="F"), L.copy(order="F"), z.copy(order="F"))
+    O.residual(po)
+    h0 = {k: getattr(po.levels[0], k).copy(order="F") for k in ("L", "D", "iD", "x", "r")}
+    rhs, rhsM = X.vcycle_rhs(h0, po.levels[1].shape)
+    O.Vcycle(po, 0)
+    h1 = {k: getattr(po.levels[1], k).copy(order="F") for k in ("L", "D", "x", "r")}
+    v, M = X.coarse_defect(h1, rhs, rhsM)
+    check("coarse_inv", np.zeros(len(v)), v, M, T, f"coarse r+Ax {np.dtype(T).name}", control=False)
+    h1["L"][tuple(n // 2 for n in po.levels[1].shape) + (0,)] *= T(1.25)
+    assert fails("coarse_inv", np.zeros(len(v)), *X.coarse_defect(h1, rhs, rhsM), T)
 
 
 @pytest.mark.parametrize("T", TYPES)

@@ -32,7 +32,19 @@ LD = np.longdouble
 # largest ratio measured (oracle 1.13, kernels 1.80).
 K = {"conv_diff": 8, "div": 4, "bdim_f": 4, "bdim_u": 8, "flux_out": 4, "accelerate": 1, "scale_u": 1, "diag": 4,
      "iD": 8, "mult": 4, "residual": 8, "jacobi": 8, "alpha": 16, "pcg": 16, "restrict": 4, "restrictL": 4,
-     "prolongate": 0}
+     "prolongate": 0,
+     # the corrector's f after a whole mom_step! (mom_f below): conv_diff! within 8 eps of its M, which |dt| scales; the
+     # acceleration and its rounding to T 1 (r + g, eps/2 of |r| + |g| twice); f = u0 + dt*f - V three roundings of at
+     # most eps/2 of M each, rounded up to 3: 8 + 1 + 3
+     "mom_f": 12,
+     # the coarse V-cycle tail (wl_coarse.h) against its per-level launches: |on - off| <= K * eps_T * (the level's scale
+     # of that array, test_xref_step_gpu.py).  Not the rounding bound of one expression: the two group pcg!'s Float64 dot
+     # sums differently, so alpha and beta may round apart by an ulp of T and that travels through six iterations and up
+     # the levels.  Largest measured: Float32 0 (bit-identical), Float64 4.95; K = 16 is the 3x margin of the others
+     "coarse_tail": 16,
+     # r + A x = rhs on the level below Vcycle!'s: x and r take 8 updates (smoother, prolongate!+increment!, six pcg!
+     # iterations), each rounds x, A*delta (mult: 4) and r; 8 * (1 + 4 + 1) = 48, rounded up to 64
+     "coarse_inv": 64}
 
 
 def eps(T) -> float:
@@ -209,6 +221,18 @@ def bdim_u(C: Cells, c: int, dt):
     return u + LD(0.5) * s + V + mu0 * f0, abs(u) + LD(0.5) * Ms + abs(V) + abs(mu0) * M0
 
 
+def mom_f(C: Cells, c: int, nu, dt, g=0.0, perdir=()):
+    """Flow.jl:164-166 + :133: the f that one mom_step! leaves behind -- the corrector's BDIM! value
+        f = u_start + dt * (conv_diff(u') + g_corr) - V
+    at C's cells.  C reads "u" = u' (the predictor's projected velocity, ghost cells as BC! left them), "us" = u_start (the
+    velocity the step started from: Flow.jl:154 copied it into u0) and "V".  M composes the bounds of conv_diff, accelerate
+    and bdim_f: |u_start| + |dt| * (M_conv_diff + |g|) + |V|."""
+    cv, cM = conv_diff(C, c, nu, perdir)
+    us, V = C("us", (), c), C("V", (), c)
+    dt, g = LD(dt), LD(g)
+    return us + dt * (cv + g) - V, abs(us) + abs(dt) * (cM + abs(g)) + abs(V)
+
+
 def accelerate(C: Cells, c: int, g):
     """Flow.jl:68-70  r[..,i] .+= g_i (every cell)"""
     r = C("r", (), c)
@@ -299,10 +323,12 @@ def restrict(C: Cells, name="b"):
     return v, M
 
 
-def restrictL(C: Cells, c: int, name="b"):
-    """MultiLevelPoisson.jl:10-16,26-32 restrictL! of component c at COARSE cells (non-periodic): 0.5 * the 2^(D-1) fine
-    faces up(I,c) on 2:n-1, then BC!(a, 0) (util.jl:192-210): planes 1, 2 and N of the normal direction hold 0, every
-    other ghost cell the value of the nearest inside cell."""
+def restrictL(C: Cells, c: int, name="b", perdir=()):
+    """MultiLevelPoisson.jl:10-16,26-32 restrictL! of component c at COARSE cells: 0.5 * the 2^(D-1) fine faces up(I,c)
+    on 2:n-1, then BC!(a, 0, false, perdir) (util.jl:192-210).  Without periodic directions: planes 1, 2 and N of the
+    normal direction hold 0, every other ghost cell the value of the nearest inside cell.  With them: _restrictL_per."""
+    if perdir:
+        return _restrictL_per(C, c, name, tuple(perdir))
     D = C.D
     cl = tuple(np.clip(a, 1, n - 2) for a, n in zip(C.idx, C.N))        # tangential zero-Neumann ghosts
     v = np.zeros(len(C), LD)
@@ -319,10 +345,68 @@ def restrictL(C: Cells, c: int, name="b"):
     return np.where(wall, LD(0), LD(0.5) * v), np.where(wall, LD(0), LD(0.5) * M)
 
 
+def _restrictL_per(C: Cells, c: int, name, perdir):
+    """restrictL! with periodic directions: the inside values of the whole coarse array, then BC!'s loop over j = 1..D
+    for component c (util.jl:194-207) replayed as plane copies in that order -- a periodic j copies plane N-1 into ghost
+    plane 1 and plane 2 into ghost plane N (the normal component's plane 2 keeps its restricted value), a wall j zeroes
+    (normal) or copies the neighbour plane (tangential) -- so edges and corners hold what the reference leaves there."""
+    D, N = C.D, C.N
+    full = tuple(a.ravel(order="F") for a in np.meshgrid(*[np.arange(n) for n in N], indexing="ij"))
+    ins = np.all([(a >= 1) & (a <= n - 2) for a, n in zip(full, N)], axis=0)
+    v = np.zeros(len(full[0]), LD)
+    M = np.zeros(len(full[0]), LD)
+    for corner in np.ndindex(*(2,) * D):
+        if corner[c]:
+            continue
+        ix = tuple(np.where(ins, 2 * a - 1 + o, 0) for a, o in zip(full, corner))
+        b = Cells(full, N, C.get, C.NA).at(name, ix, c)
+        v += np.where(ins, b, 0)
+        M += np.where(ins, abs(b), 0)
+    v, M = (LD(0.5) * a.reshape(N, order="F") for a in (v, M))
+    for j in range(D):
+        sl = lambda q: tuple(q if d == j else slice(None) for d in range(D))
+        n = N[j]
+        if j in perdir:
+            pairs = ((0, n - 2), (n - 1, 1))
+        elif j == c:
+            pairs = ((0, None), (1, None), (n - 1, None))
+        else:
+            pairs = ((0, 1), (n - 1, n - 2))
+        for dst, src in pairs:
+            for a in (v, M):
+                a[sl(dst)] = 0 if src is None else a[sl(src)]
+    return v[C.idx], M[C.idx]
+
+
 def prolongate(C: Cells, name="b"):
     """MultiLevelPoisson.jl:2,34  a[I] = b[down(I)], down(I) = (I+2)÷2 (1-based): a copy, exact.  C: FINE inside cells."""
     v = C.at(name, tuple((a + 1) // 2 for a in C.idx))
     return v, abs(v)
+
+
+def vcycle_rhs(h0: dict, Nc):
+    """The right-hand side Vcycle! hands to the next level (MultiLevelPoisson.jl:72-74): restrict! of the residual after
+    one Jacobi!+increment! sweep, from the host arrays L, D, iD, r, x of the level before the call; (value, M) on every
+    cell of the coarse grid of extents Nc (0 on its ghost cells)."""
+    Ng = h0["r"].shape
+    C0 = host_cells({k: h0[k] for k in ("L", "D", "iD", "r", "x")}, N=Ng)
+    _, (rv, rM), _ = jacobi_increment(C0)
+    ins = np.all([(w >= 1) & (w <= n - 2) for w, n in zip(C0.idx, Ng)], axis=0)
+    rv, rM = (np.where(ins, a, 0).reshape(Ng, order="F") for a in (rv, rM))
+    Cc = host_cells({"v": rv, "M": rM}, N=Nc, NA=Ng)
+    insc = np.all([(w >= 1) & (w <= n - 2) for w, n in zip(Cc.idx, Nc)], axis=0)
+    return np.where(insc, restrict(Cc, "v")[0], 0), np.where(insc, restrict(Cc, "M")[0], 0)
+
+
+def coarse_defect(h: dict, rhs, rhsM):
+    """r + A x - rhs at the inside cells of a level (exact, on the stored L and D) and its bound M_rhs + |A||x|: zero in
+    exact arithmetic after any sequence of the updates x += d, r -= A d from x = 0, r = rhs (Jacobi!, prolongate! +
+    increment!, pcg!) -- whatever the dot products that chose d summed to."""
+    N = h["r"].shape
+    C = host_cells({"L": h["L"], "D": h["D"], "x": h["x"], "r": h["r"]}, N=N)
+    ins = np.all([(w >= 1) & (w <= n - 2) for w, n in zip(C.idx, N)], axis=0)
+    Ax, AM = mult(C)
+    return (C("r") + Ax - rhs)[ins], (rhsM + AM)[ins]
 
 
 def pcg1_ref(L, D, iD, r):

@@ -1,4 +1,7 @@
-"""Adversarial inputs shared by the xref checks (test_xref_cpu.py against the oracle, test_xref_gpu.py against the kernels)."""
+"""Adversarial inputs shared by the xref checks (test_xref_cpu.py against the oracle, test_xref_gpu.py and
+test_xref_step_gpu.py against the kernels)."""
+import itertools
+
 import numpy as np
 
 KINDS = ["random", "ties", "step", "scaled-up", "scaled-down"]
@@ -106,3 +109,31 @@ def samples(Ng, nrand, seed, row_step=None):
     for i, j in ((1, 1), (n0 // 2, n1 // 3), (n0 - 2, 1), (n0 - 2, n1 - 2)):
         out.append((np.full(k.size, i), np.full(k.size, j), k))
     return tuple(np.concatenate([o[d] for o in out]).astype(np.int64) for d in range(3))
+
+
+def step_fields(Ng, T, seed, block):
+    """Start of a mom_step! check on a grid of extents Ng (ghosts included): a non-uniform velocity u (x component
+    1 + 0.3*random, the others 0.3*random) and a synthetic body inside `block` (one slice per dimension, clear of the
+    ghost cells): mu0 in [0.3, 1], mu1 in [-0.3, 0.3], V in [-0.4, 0.4] there -- the rows through it are busy, every other
+    row is body-free (mu0 = 1, mu1 = 0, V = 0).  mu0 carries BC!(mu0, 0): zero normal coefficient on planes 1, 2 and N."""
+    D = len(Ng)
+    rng = np.random.default_rng(seed)
+    T = np.dtype(T)
+    u = 0.3 * (2 * rng.random(Ng + (D,)) - 1)
+    u[..., 0] += 1.0
+    mu0 = np.ones(Ng + (D,))
+    mu1 = np.zeros(Ng + (D, D))
+    V = np.zeros(Ng + (D,))
+    nb = tuple(s.stop - s.start for s in block)
+    mu0[block] = 0.3 + 0.7 * rng.random(nb + (D,))
+    mu1[block] = 0.3 * (2 * rng.random(nb + (D, D)) - 1)
+    V[block] = 0.4 * (2 * rng.random(nb + (D,)) - 1)
+    for c in range(D):
+        for q in (0, 1, Ng[c] - 1):
+            mu0[tuple(q if d == c else slice(None) for d in range(D)) + (c,)] = 0
+    return {k: np.asfortranarray(a.astype(T)) for k, a in (("u", u), ("mu0", mu0), ("mu1", mu1), ("V", V))}
+
+
+def periodic_subsets(D):
+    """every non-empty set of periodic directions of a D-dimensional grid"""
+    return [p for n in range(1, D + 1) for p in itertools.combinations(range(D), n)]
