@@ -320,6 +320,23 @@ int wl_metric(wl_dtype t, const wl_grid *g, int kind, void *out, const void *u, 
 int wl_meanflow_update(wl_dtype t_flow, wl_dtype t_acc, const wl_grid *g, const void *u, const void *p, const wl_grid *ga, void *U,
                        void *P, void *UU, void *pp, double eps, int first);
 
+/* ------------------------------------------------------------------ point probes and tracers (waterlily_amd/probes.py)
+ * interp(x, arr)  src/util.jl:238-257.  x_dev: m*D doubles, point-major, 1-based index coordinates (global z).
+ * ncomp == 0: scalar field; ncomp == D: staggered vector field.  Row q of the result at out_dev + q*ldo (ldo >= max(1,ncomp)).
+ * With i = floor(x), y = x - i: sum over the 2^D corners J in CartesianIndices order of a[J] * prod_d(J_d == i_d ? 1-y_d : y_d),
+ * the product in d order, all in double (Float64 results for either T); component c of a vector field is sampled at
+ * x + 0.5 e_c (util.jl:253-256).  A corner of weight exactly 0 is not read; a weighted corner outside the array (ghosts
+ * included) gives NaN.  z-slabs: each (point, component) is written by the rank owning its floor plane (the first / last rank
+ * for the z ghost planes of a ring and for planes outside the array), every other rank writes 0: a sum over the ranks is the
+ * value.  Reads the first halo plane of the owner.  Asynchronous. */
+int wl_interp(wl_dtype t, const wl_grid *g, const void *a, int ncomp, const double *x_dev, int64_t m, double *out_dev,
+              int64_t ldo);
+/* one frozen-field Heun step of m tracers (not on decomposed grids): k1 = u(x), xs = x + dt k1, k2 = u(xs),
+ * x <- x + 0.5 dt (k1 + k2) with u interpolated as wl_interp does; directions in perdir_mask wrap xs and x into
+ * [1.5, N_d + 1.5); a particle leaving [1.5, N_d + 1.5] in another direction or meeting a NaN velocity gets NaN coordinates
+ * (dead) and is skipped from then on.  dt finite and >= 0.  A z-slab grid is refused (WL_E_STATE).  Asynchronous. */
+int wl_tracer_advance(wl_dtype t, const wl_grid *g, const void *u, double *x_dev, int64_t m, double dt, int perdir_mask);
+
 /* ------------------------------------------------------------------ snapshots (VTK write / restart, ext/WaterLilyWriteVTKExt.jl:57-66,
  * ext/WaterLilyReadVTKExt.jl:28-45).  The reference copies whole fields to the host (`a.flow.u |> Array`) and permutes the vector
  * components to the front there (components_first, :79).  Here the field's LOCAL planes klo..khi are packed on the device into

@@ -161,6 +161,15 @@ function L₂(a::HIPArray{T}) where T                                           
     o = Ref{Cdouble}()
     chk(ccall((:wl_L2_inside, lib), Cint, (Cint, Ref{WlGrid}, Ptr{Cvoid}, Ref{Cdouble}), dtype(T), grid(a), a.ptr, o)); o[]
 end
+# interp(x, arr)  src/util.jl:232-257: ONE wl_interp call (Float64 result, NaN out of range) instead of 2^D scalar reads per
+# component; arr is a scalar field (ndims == D) or a staggered vector field (the reference's dispatch)
+function WaterLily.interp(x::SVector{D}, arr::HIPArray{T}) where {D,T}
+    nc = ndims(arr) == D ? 0 : D
+    xd = HIPArray(Vector{Float64}(collect(x))); od = HIPArray{Float64,1}((max(1, nc),))
+    chk(ccall((:wl_interp, lib), Cint, (Cint, Ref{WlGrid}, Ptr{Cvoid}, Cint, Ptr{Cdouble}, Int64, Ptr{Cdouble}, Int64),
+              dtype(T), grid(arr, D), arr.ptr, Cint(nc), xd.ptr, Int64(1), od.ptr, Int64(max(1, nc))))
+    o = Array(od); nc == 0 ? o[1] : SVector{D}(o)
+end
 function apply!(f, c::HIPArray)                                                                # src/util.jl:170-172
     h = Array(c); apply!(f, h); copyto!(c, h)                                                  # user closure: host, then upload
 end

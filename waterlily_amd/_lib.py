@@ -153,6 +153,8 @@ def lib() -> C.CDLL:
         "wl_vforce": (i, [i, gp, vp, vp, vp, i64, d, dp]),
         "wl_pmoment": (i, [i, gp, vp, vp, vp, i64, dp, dp]),
         "wl_meanflow_update": (i, [i, i, gp, vp, vp, gp, vp, vp, vp, vp, d, i]),
+        "wl_interp": (i, [i, gp, vp, i, vp, i64, vp, i64]),
+        "wl_tracer_advance": (i, [i, gp, vp, vp, i64, d, i]),
         "wl_snapshot_pack": (i, [i, gp, vp, i, i, i, i, vp]),
         "wl_snapshot_unpack": (i, [i, gp, vp, i, i, i, i, vp]),
         "wl_set_option": (i, [i, i]),

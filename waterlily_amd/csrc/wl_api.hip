@@ -13,6 +13,7 @@
 #include "wl_coarse.h"
 #include "wl_measure.h"
 #include "wl_stats.h"
+#include "wl_probe.h"
 
 namespace wl {
 
@@ -1428,6 +1429,29 @@ int wl_meanflow_update(wl_dtype t_flow, wl_dtype t_acc, const wl_grid *g, const 
     }
     if (g->D == 2) return op_meanflow<double, double, 2>(gf, gacc, (const double *)u, (const double *)p, (double *)U, (double *)P, (double *)UU, (double *)pp, eps, first);
     return op_meanflow<double, double, 3>(gf, gacc, (const double *)u, (const double *)p, (double *)U, (double *)P, (double *)UU, (double *)pp, eps, first);
+}
+int wl_interp(wl_dtype t, const wl_grid *g, const void *a, int ncomp, const double *x_dev, int64_t m, double *out_dev,
+              int64_t ldo) {
+    WL_TRY(check_grid(g));
+    if (t != WL_F32 && t != WL_F64) return fail(WL_E_ARG, "wl_interp: unknown dtype", __FILE__, __LINE__);
+    if (!a || !x_dev || !out_dev) return fail(WL_E_ARG, "wl_interp: null field, points or output", __FILE__, __LINE__);
+    if (ncomp != 0 && ncomp != g->D) return fail(WL_E_ARG, "wl_interp: ncomp must be 0 (scalar) or D (staggered vector)", __FILE__, __LINE__);
+    if (m < 0) return fail(WL_E_ARG, "wl_interp: negative number of points", __FILE__, __LINE__);
+    if (ldo < (ncomp > 1 ? ncomp : 1)) return fail(WL_E_ARG, "wl_interp: ldo smaller than one row of the result", __FILE__, __LINE__);
+    const G gg = mkG(g);
+    WL_DISPATCH(t, g->D, (op_interp<T, DD>(gg, (const T *)a, ncomp, x_dev, m, out_dev, ldo)));
+}
+int wl_tracer_advance(wl_dtype t, const wl_grid *g, const void *u, double *x_dev, int64_t m, double dt, int perdir_mask) {
+    WL_TRY(check_grid(g));
+    if (t != WL_F32 && t != WL_F64) return fail(WL_E_ARG, "wl_tracer_advance: unknown dtype", __FILE__, __LINE__);
+    if (!u || !x_dev) return fail(WL_E_ARG, "wl_tracer_advance: null velocity or positions", __FILE__, __LINE__);
+    if (m < 0) return fail(WL_E_ARG, "wl_tracer_advance: negative number of particles", __FILE__, __LINE__);
+    if (!(std::isfinite(dt) && dt >= 0.0)) return fail(WL_E_ARG, "wl_tracer_advance: dt must be finite and >= 0", __FILE__, __LINE__);
+    if (perdir_mask < 0 || perdir_mask >= (1 << g->D)) return fail(WL_E_ARG, "wl_tracer_advance: bad perdir_mask", __FILE__, __LINE__);
+    if (g->D == 3 && g->nzg > 0)
+        return fail(WL_E_STATE, "wl_tracer_advance: tracers on a z-slab decomposition are not supported", __FILE__, __LINE__);
+    const G gg = mkG(g);
+    WL_DISPATCH(t, g->D, (op_tracer_advance<T, DD>(gg, (const T *)u, x_dev, m, dt, perdir_mask)));
 }
 int wl_pforce(wl_dtype t, const wl_grid *g, const void *p, const int64_t *idx, const double *nds, int64_t nband,
               double out[3]) {
