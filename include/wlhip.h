@@ -306,6 +306,22 @@ enum { WL_M_KE = 0, WL_M_CURL = 1, WL_M_OMAG = 2, WL_M_OTHETA = 3, WL_M_LAMBDA2 
 int wl_metric(wl_dtype t, const wl_grid *g, int kind, void *out, const void *u, int ipar, const double par[3],
               const double par2[3]);
 
+/* ------------------------------------------------------------------ volume integrals (Integrals, waterlily_amd/integrals.py)
+ * One sweep over u: sums and maxima over the cells I of inside(p) (z-slabs: this rank's owned interior planes; nothing is
+ * communicated, the caller combines the ranks' rows), d(i,j) = the reference's ∂(i,j,I,u) (src/Metrics.jl:28-30).  row_dev
+ * receives 6 + D doubles (device memory):
+ *   0 E = sum ke(I,u,U)    1 Z = sum |omega|^2 / 2 (D == 2: omega_3 = d(2,1) - d(1,2))    2 S = sum S_ij S_ij, S = sym(d)
+ *   3 div2 = sum (sum_i d(i,i))^2    4 divmax = max |sum_i d(i,i)|    5 umax = max_i |u[I,i]|
+ *   6.. P_i = sum (u[I,i] + u[I+d_i,i]) / 2
+ * Every operand is converted to double before the first operation, for either T; sums and maxima are reduced in a fixed
+ * order (same field, same bits; no floating-point atomics).  NaN in u gives NaN in the sums that read it; the maxima skip
+ * NaN operands (the comparison of wl_max) and are 0 over an empty range.  No body mask: solid and fluid cells alike.
+ * U: the background velocity of ke (D values read).  Reads the ghost cells around the interior and, on a z-slab, the first
+ * halo plane on each side (mom_step! leaves them current).  Asynchronous: two launches on the library's stream, nothing
+ * allocated after the library's first reduction.  WaterLily v1.3 has no such function to override: the entry point is there
+ * for a later binding. */
+int wl_flow_integrals(wl_dtype t, const wl_grid *g, const void *u, const double U[3], double *row_dev);
+
 /* ------------------------------------------------------------------ time-averaged statistics (MeanFlow, waterlily_amd/stats.py)
  * One update of running means of u and p, and optionally of the velocity covariance (Reynolds stress) and the pressure
  * variance, over EVERY element of the local arrays (ghost cells and z-slab halo planes included; row padding untouched):

@@ -152,6 +152,7 @@ def lib() -> C.CDLL:
         "wl_pforce": (i, [i, gp, vp, vp, vp, i64, dp]),
         "wl_vforce": (i, [i, gp, vp, vp, vp, i64, d, dp]),
         "wl_pmoment": (i, [i, gp, vp, vp, vp, i64, dp, dp]),
+        "wl_flow_integrals": (i, [i, gp, vp, dp, vp]),
         "wl_meanflow_update": (i, [i, i, gp, vp, vp, gp, vp, vp, vp, vp, d, i]),
         "wl_interp": (i, [i, gp, vp, i, vp, i64, vp, i64]),
         "wl_tracer_advance": (i, [i, gp, vp, vp, i64, d, i]),

@@ -14,6 +14,7 @@
 #include "wl_measure.h"
 #include "wl_stats.h"
 #include "wl_probe.h"
+#include "wl_integrals.h"
 
 namespace wl {
 
@@ -1402,6 +1403,12 @@ int wl_metric(wl_dtype t, const wl_grid *g, int kind, void *out, const void *u, 
     if (kind < 0 || kind > WL_M_LAMBDA2 || (kind >= WL_M_OMAG && g->D != 3) || (kind == WL_M_CURL && (ipar < 0 || ipar > 2)))
         return fail(WL_E_ARG, "wl_metric: bad kind/component for this dimension", __FILE__, __LINE__);
     WL_DISPATCH(t, g->D, (op_metric<T, DD>(gg, kind, (T *)out, (const T *)u, ipar, par, par2)));
+}
+int wl_flow_integrals(wl_dtype t, const wl_grid *g, const void *u, const double U[3], double *row_dev) {
+    if (!g || !u || !U || !row_dev) return fail(WL_E_ARG, "wl_flow_integrals: null grid, u, U or row", __FILE__, __LINE__);
+    if (g->D != 2 && g->D != 3) return fail(WL_E_ARG, "wl_flow_integrals: D must be 2 or 3", __FILE__, __LINE__);
+    WL_GS();
+    WL_DISPATCH(t, g->D, (op_integrals<T, DD>(gg, (const T *)u, U, S.partials, row_dev)));
 }
 int wl_meanflow_update(wl_dtype t_flow, wl_dtype t_acc, const wl_grid *g, const void *u, const void *p, const wl_grid *ga, void *U,
                        void *P, void *UU, void *pp, double eps, int first) {

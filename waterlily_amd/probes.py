@@ -33,13 +33,21 @@ def _points(x, D: Optional[int] = None) -> np.ndarray:
     return np.ascontiguousarray(X.reshape(-1, X.shape[-1]))
 
 
-def _rank_sum(v: np.ndarray, slab) -> np.ndarray:
-    """Sum of the ranks' arrays (every entry is non-zero on at most its owner), in rank order, at the host."""
+def _rank_parts(v: np.ndarray, slab) -> list:
+    """The ranks' arrays in rank order, at the host (one all-gather; [v] when not decomposed)."""
     if slab is None or slab.size == 1:
-        return v
+        return [v]
     import torch.distributed as dist
     parts = [None] * slab.size
     dist.all_gather_object(parts, v)
+    return parts
+
+
+def _rank_sum(v: np.ndarray, slab) -> np.ndarray:
+    """Sum of the ranks' arrays (every entry is non-zero on at most its owner), in rank order, at the host."""
+    parts = _rank_parts(v, slab)
+    if len(parts) == 1:
+        return v
     out = parts[0].copy()
     for p in parts[1:]:
         out += p
