@@ -98,7 +98,7 @@ int wl_comm_init_loopback(int rank, int nranks);
  * may shm_unlink the name).  From then on the library sums its scalars through that block of pinned host memory -- one
  * system-scope store + one poll per peer, combined in rank order (bit-identical on every rank) -- instead of one RCCL
  * all-reduce per value; halo planes and the coarse-level all-gather stay on RCCL.  Waits are bounded in wall-clock time
- * (wl_set_option(26), seconds; 0 = unbounded): a rank that gives up reports WL_E_STATE at the caller's next synchronising
+ * (WL_OPT_MBOX_TIMEOUT_S, seconds; 0 = unbounded): a rank that gives up reports WL_E_STATE at the caller's next synchronising
  * call.  Optional: without it scalars use ncclAllReduce. */
 int wl_comm_mailbox(const char *shm_name, int create);
 int wl_comm_mailbox_off(void);          /* back to the communicator's all-reduce (every rank must call it at the same point) */
@@ -170,7 +170,7 @@ int wl_mg_destroy(wl_mg *m);
 /* update!(ml)                         src/MultiLevelPoisson.jl:62-68 (src/Poisson.jl:46 for one level) */
 int wl_mg_update(wl_mg *m);
 /* Introspection: how many interior x-rows of `level` carry one coefficient value on all their faces (the 7-point kernels
- * skip the loads of L there, see wl_set_option key 9) out of how many owned interior rows.  0 for D==2. */
+ * skip the loads of L there, see WL_OPT_ROW_CONST_L) out of how many owned interior rows.  0 for D==2. */
 int wl_mg_uniform_rows(wl_mg *m, int level, long long *n_uniform, long long *n_rows);
 /* mult!(p,x): p.z = A x               src/Poisson.jl:62-68 */
 int wl_mg_mult(wl_mg *m, int level, void *x);
@@ -273,7 +273,7 @@ int wl_project(wl_flow *a, wl_mg *b, double dt, double w, int *n_iter);
  * no-op, :73).  dt_next receives CFL(a); n_iter[2] the two entries pushed onto pois.n.
  * The u0 ARRAY is scratch across the call, as in the reference (it is overwritten by `a.u⁰ .= a.u` before anything reads
  * it, :154): on return it holds either the velocity the step started from (the reference's copy) or -- 3-D, no periodic
- * direction, no convective exit, wl_set_option(27) -- the predictor's velocity u', because there the two velocity arrays
+ * direction, no convective exit, WL_OPT_BDIM_IN_CONVDIFF -- the predictor's velocity u', because there the two velocity arrays
  * take turns instead of being copied (the predictor reads u and writes u' into u0, the corrector writes the new velocity
  * back into u).  u, p, f, sigma, the time step and the V-cycle counts are the same bits either way. */
 int wl_mom_step(wl_flow *a, wl_mg *b, double dt, const double U[3], const double *acc_pred,
@@ -366,51 +366,78 @@ int wl_snapshot_unpack(wl_dtype t, const wl_grid *g, void *a, int ncomp, int ntu
  * Every key selects between the form of an operator the reference writes and a traffic-saving form of it that produces the
  * same bits (tests flip them one by one, and all at once); a few are tuning values.  The defaults are the measured winners;
  * round 4 retired the keys whose alternative was a recorded loss (11, 12, 20, 21, 24, 25, 28: DESIGN.md, measured dead ends).
- * key 0: 1 = use the 16-B-vectorised z-marching 7-point kernel where it applies (default), 0 = generic range kernel
- * key 1: 1 = fused V-cycle smoothers (default), 0 = the reference's two-pass Jacobi!/increment!/prolongate!
- * key 2: 1 = LDS-tiled marching conv_diff kernel (default), 0 = generic gather kernel
- * key 3: 1 = BDIM! uses the body-free row flags (default), 0 = general path everywhere
- * key 4: rows per thread of the vectorised 7-point kernel (a 256-thread workgroup covers 4x that many rows): 1, 2, or
- *        0 (default) = 2 on levels of >= 2^26 interior cells with an even y extent, else 1.  Same values either way.
- * key 5: != 0 = 16-B vectorised streaming pcg kernels (default), 0 = scalar range kernels
- * key 6: 1 = multigrid levels <= 4096 cells run as one single-workgroup launch per V-cycle (default), 0 = per-op launches
- * key 7: 1 = BC! as one closed-form launch (default), 0 = the reference's sequence of plane loops
- * key 8: 1 = pcg! applies x += alpha*eps in the direction kernel instead of the update kernel (default; one array
- *        pass less per iteration, identical values), 0 = in the update kernel as the reference orders it
- * key 9: 1 = the 7-point kernels skip the loads of L in rows whose face coefficients are all one number (rows clear
- *        of the body and the domain faces; constants recorded by wl_mg_update) (default), 0 = always load L
- * key 10: 1 = inside solver! the start of pcg! (eps = r*iD, rho) is evaluated by the prolongate!+increment! kernel that
- *         has just produced r (default), 0 = by pcg!'s own first kernel
- * key 13: 1 = pcg! does not store z' = r*iD, the direction kernel recomputes it (default), 0 = stored as in the reference
- * key 14: 1 = inside mom_step! the predictor's closing `x ./= dt` and the corrector's opening `x .*= 0.5dt`
- *         (Flow.jl:144,139) are one pass over x, each rounding kept (default), 0 = two passes
- * key 15: 1 = on levels of at most 2^25 cells pcg!'s dot products are finished by the kernel that follows (no
- *         one-workgroup finalize launches inside a pcg! call; single rank) (default), 2 = on every level, 0 = separate
- *         finalize launch after every dot product
- * keys 16, 17: grid size of the 7-point / streaming vector kernels in units of 1024 workgroups (defaults 4 / 16: measured
- *         at 512^3, the streaming kernels gain 3-6 % from shorter z-chunks, the 7-point kernels do not)
- * key 18: 1 = conv_diff! evaluates each interior face flux once and shares it between the two cells (shared-flux LDS kernel
- *         on the tiles / planes whose y and z faces are all interior; 64x8 tiles in Float32, 64x4 in Float64) (default),
- *         0 = every cell gathers its six fluxes
- * key 19: 1 = on levels of 2^22 .. 2^26 cells pcg! does not store z = A*eps: its update kernel is a second 7-point kernel over
- *         eps that forms the same A*eps again and applies r -= alpha*(A*eps) (default; 3-D vector kernels), 3 = on every
- *         level below 2^26 cells, 2 = on every level, 0 = the mult kernel always stores z
- * key 22: 1 = inside wl_mom_step / wl_project (3-D, one device) z = div(u) is formed by the residual! kernel itself, the
- *         z array is neither written nor read (default), 0 = separate div pass
- * key 23: 1 = inside wl_mom_step (3-D, x not periodic) the x-ghost cells of the interior rows that BC!(u,U) sets are
- *         written by the kernel that has just produced the row (BDIM!, the velocity correction); the BC launch that
- *         follows covers the y and z planes only (default), 0 = BC! writes all six planes
- * key 26: bound of a mailbox all-reduce's wait for a peer in SECONDS of the device's wall clock (default 600; 0 = unbounded,
- *         like a collective)
- * key 27: 1 = inside wl_mom_step (3-D, no periodic direction, no convective exit) the conv_diff! kernels finish BDIM!
- *         (Flow.jl:134, scale_u! :166) on the body-free x-rows themselves: the row's new velocity is stored from the registers
- *         that hold f, V is not read there, and no separate pass over those rows runs (6T + 9T per cell and step less);
- *         the u0 array holds u' on return (see wl_mom_step) (default), 0 = separate BDIM! pass, u0 = the copy of u
- * key 30: 1 = consecutive marching kernels sweep their tiles in opposite directions, each XCD starting on the lines the
- *         kernel before it touched last (L2 / Infinity Cache) (default), 0 = always ascending.  Same bits either way.
- * key 31: 1 = inside the one-workgroup bottom of the V-cycle (levels of <= 4096 cells) pcg! keeps its level in registers and
- *         LDS for the whole call (default), 0 = every phase goes through global memory.  Same bits either way.
- * Any other key: WL_E_ARG. */
+ * A key is one of the WL_OPT_* numbers below; any other key: WL_E_ARG.  The numbers are part of the ABI: 11, 12, 20, 21, 24,
+ * 25, 28, 29 belonged to retired keys and are never to be reused. */
+enum {
+    /* 1 = use the 16-B-vectorised z-marching 7-point kernel where it applies (default), 0 = generic range kernel */
+    WL_OPT_STENCIL7_VEC = 0,
+    /* 1 = fused V-cycle smoothers (default), 0 = the reference's two-pass Jacobi!/increment!/prolongate! */
+    WL_OPT_SMOOTH_FUSED = 1,
+    /* 1 = LDS-tiled marching conv_diff kernel (default), 0 = generic gather kernel */
+    WL_OPT_CONVDIFF_TILED = 2,
+    /* 1 = BDIM! uses the body-free row flags (default), 0 = general path everywhere */
+    WL_OPT_BDIM_ROWFLAGS = 3,
+    /* rows per thread of the vectorised 7-point kernel (a 256-thread workgroup covers 4x that many rows): 1, 2, or 0 (default)
+     * = 2 on levels of >= 2^26 interior cells with an even y extent, else 1.  Same values either way. */
+    WL_OPT_STENCIL7_ROWS = 4,
+    /* != 0 = 16-B vectorised streaming pcg kernels (default), 0 = scalar range kernels */
+    WL_OPT_PCG_VEC = 5,
+    /* 1 = multigrid levels <= 4096 cells run as one single-workgroup launch per V-cycle (default), 0 = per-op launches */
+    WL_OPT_COARSE_TAIL = 6,
+    /* 1 = BC! as one closed-form launch (default), 0 = the reference's sequence of plane loops */
+    WL_OPT_BC_FUSED = 7,
+    /* 1 = pcg! applies x += alpha*eps in the direction kernel instead of the update kernel (default; one array pass less per
+     * iteration, identical values), 0 = in the update kernel as the reference orders it */
+    WL_OPT_PCG_DEFER_X = 8,
+    /* 1 = the 7-point kernels skip the loads of L in rows whose face coefficients are all one number (rows clear of the body
+     * and the domain faces; constants recorded by wl_mg_update) (default), 0 = always load L */
+    WL_OPT_ROW_CONST_L = 9,
+    /* 1 = inside solver! the start of pcg! (eps = r*iD, rho) is evaluated by the prolongate!+increment! kernel that has just
+     * produced r (default), 0 = by pcg!'s own first kernel */
+    WL_OPT_PCG_START_FUSED = 10,
+    /* 1 = pcg! does not store z' = r*iD, the direction kernel recomputes it (default), 0 = stored as in the reference */
+    WL_OPT_PCG_RECOMPUTE_PRECOND = 13,
+    /* 1 = inside mom_step! the predictor's closing `x ./= dt` and the corrector's opening `x .*= 0.5dt` (Flow.jl:144,139) are
+     * one pass over x, each rounding kept (default), 0 = two passes */
+    WL_OPT_SCALE_CHAIN = 14,
+    /* 1 = on levels of at most 2^25 cells pcg!'s dot products are finished by the kernel that follows (no one-workgroup
+     * finalize launches inside a pcg! call; single rank) (default), 2 = on every level, 0 = separate finalize launch after
+     * every dot product */
+    WL_OPT_PCG_DOTS_IN_KERNEL = 15,
+    /* grid size of the 7-point / streaming vector kernels in units of 1024 workgroups (defaults 4 / 16: measured at 512^3, the
+     * streaming kernels gain 3-6 % from shorter z-chunks, the 7-point kernels do not) */
+    WL_OPT_STENCIL7_GRID_K = 16,
+    WL_OPT_STREAM_GRID_K = 17,
+    /* 1 = conv_diff! evaluates each interior face flux once and shares it between the two cells (shared-flux LDS kernel on the
+     * tiles / planes whose y and z faces are all interior; 64x8 tiles in Float32, 64x4 in Float64) (default), 0 = every cell
+     * gathers its six fluxes */
+    WL_OPT_CONVDIFF_SHARED_FLUX = 18,
+    /* 1 = on levels of 2^22 .. 2^26 cells pcg! does not store z = A*eps: its update kernel is a second 7-point kernel over eps
+     * that forms the same A*eps again and applies r -= alpha*(A*eps) (default; 3-D vector kernels), 3 = on every level below
+     * 2^26 cells, 2 = on every level, 0 = the mult kernel always stores z */
+    WL_OPT_PCG_RECOMPUTE_AEPS = 19,
+    /* 1 = inside wl_mom_step / wl_project (3-D, one device) z = div(u) is formed by the residual! kernel itself, the z array is
+     * neither written nor read (default), 0 = separate div pass */
+    WL_OPT_DIV_IN_RESIDUAL = 22,
+    /* 1 = inside wl_mom_step (3-D, x not periodic) the x-ghost cells of the interior rows that BC!(u,U) sets are written by the
+     * kernel that has just produced the row (BDIM!, the velocity correction); the BC launch that follows covers the y and z
+     * planes only (default), 0 = BC! writes all six planes */
+    WL_OPT_XGHOST_IN_KERNEL = 23,
+    /* bound of a mailbox all-reduce's wait for a peer in SECONDS of the device's wall clock (default 600; 0 = unbounded, like a
+     * collective) */
+    WL_OPT_MBOX_TIMEOUT_S = 26,
+    /* 1 = inside wl_mom_step (3-D, no periodic direction, no convective exit) the conv_diff! kernels finish BDIM! (Flow.jl:134,
+     * scale_u! :166) on the body-free x-rows themselves: the row's new velocity is stored from the registers that hold f, V is
+     * not read there, and no separate pass over those rows runs (6T + 9T per cell and step less); the u0 array holds u' on
+     * return (see wl_mom_step) (default), 0 = separate BDIM! pass, u0 = the copy of u */
+    WL_OPT_BDIM_IN_CONVDIFF = 27,
+    /* 1 = consecutive marching kernels sweep their tiles in opposite directions, each XCD starting on the lines the kernel
+     * before it touched last (L2 / Infinity Cache) (default), 0 = always ascending.  Same bits either way. */
+    WL_OPT_SWEEP_ALTERNATE = 30,
+    /* 1 = inside the one-workgroup bottom of the V-cycle (levels of <= 4096 cells) pcg! keeps its level in registers and LDS
+     * for the whole call (default), 0 = every phase goes through global memory.  Same bits either way. */
+    WL_OPT_COARSE_PCG_RESIDENT = 31,
+};
 int wl_set_option(int key, int value);
 int wl_get_option(int key, int *value);
 

@@ -21,6 +21,7 @@ import LinearAlgebra
 using LinearAlgebra: I, inv
 
 const lib = get(ENV, "WLHIP_LIB", "libwlhip.so")
+const WL_OPT_MBOX_TIMEOUT_S = Cint(26)   # include/wlhip.h: bound of a mailbox wait in seconds
 
 # ---------------------------------------------------------------------------------------------- plumbing
 struct WlGrid            # == wl_grid
@@ -445,11 +446,11 @@ function init_slabs!(bcast, rank::Integer, nranks::Integer; device=rank, allmin=
     rank == 0 && rm("/dev/shm" * nm; force=true)       # (the mappings keep the memory alive)
     if ok == 1                                         # self-test with a short bound before the run depends on it
         keep = Ref{Cint}()
-        chk(ccall((:wl_get_option, lib), Cint, (Cint, Ref{Cint}), 26, keep))
-        chk(ccall((:wl_set_option, lib), Cint, (Cint, Cint), 26, 10))
+        chk(ccall((:wl_get_option, lib), Cint, (Cint, Ref{Cint}), WL_OPT_MBOX_TIMEOUT_S, keep))
+        chk(ccall((:wl_set_option, lib), Cint, (Cint, Cint), WL_OPT_MBOX_TIMEOUT_S, 10))
         v = Cdouble[rank + 1]
         good = ccall((:wl_allreduce, lib), Cint, (Ptr{Cdouble}, Cint, Cint), v, 1, 0) == 0 && v[1] == nranks * (nranks + 1) / 2
-        chk(ccall((:wl_set_option, lib), Cint, (Cint, Cint), 26, keep[]))
+        chk(ccall((:wl_set_option, lib), Cint, (Cint, Cint), WL_OPT_MBOX_TIMEOUT_S, keep[]))
         ok = allmin(good ? 1 : 0)
     end
     ok == 1 || chk(ccall((:wl_comm_mailbox_off, lib), Cint, ()))   # all or nothing: every rank takes the same path

@@ -8,8 +8,8 @@ usage: longparity.py <c1|c2|NxNxN|torus:N|moving:N|pbox:N> <f32|f64> <steps> [ev
   pbox:N = a sphere in a 2N x N x N box, periodic in y and z (round 4: the whole-array reductions of the reference -- sigma's
   flux scratch in the ghost cells times eps's periodic copies -- on a long horizon)
   self KEY A B: instead of the oracle, a SECOND HIP simulation stepped with wl_set_option(KEY, B) next to the first with
-  wl_set_option(KEY, A) -- e.g. `self 16 16 8` regroups the Float64 partial sums of every dot product (last-bit
-  perturbations): how fast does the flow itself amplify rounding differences?"""
+  wl_set_option(KEY, A), KEY a name or a number -- e.g. `self STENCIL7_GRID_K 16 8` regroups the Float64 partial sums of every
+  dot product (last-bit perturbations): how fast does the flow itself amplify rounding differences?"""
 import os
 import sys
 
@@ -25,7 +25,7 @@ case, tname, steps = sys.argv[1], sys.argv[2], int(sys.argv[3])
 every = int(sys.argv[4]) if len(sys.argv) > 4 else max(1, steps // 25)
 selfcmp = None
 if len(sys.argv) > 8 and sys.argv[5] == "self":
-    selfcmp = (int(sys.argv[6]), int(sys.argv[7]), int(sys.argv[8]))
+    selfcmp = (S.opt_key(sys.argv[6]), int(sys.argv[7]), int(sys.argv[8]))
 
 
 class _Twin:
@@ -72,7 +72,7 @@ if selfcmp:
     body2 = copy.deepcopy(sh.body)
     s2 = S.Simulation(dims, U, sh.L, U=sh.U, nu=sh.flow.nu, body=body2, T=T)
     so = _Twin(s2)
-print(f"# {case} {dims} {tname} Re={Re:g}: " + (f"HIP with option[{selfcmp[0]}]={selfcmp[2]} vs HIP with option[{selfcmp[0]}]={selfcmp[1]}" if selfcmp else "oracle (CPU) vs HIP")
+print(f"# {case} {dims} {tname} Re={Re:g}: " + (f"HIP with {S.opt_name(selfcmp[0])} = {selfcmp[2]} vs HIP with {S.opt_name(selfcmp[0])} = {selfcmp[1]}" if selfcmp else "oracle (CPU) vs HIP")
       + f", remeasure={str(remeasure).lower()}")
 print("# step  V-cycles(oracle)  V-cycles(HIP)  d(dt)/dt   max|du|/U   max|dp|/max|p|   force_x(oracle)  force_x(HIP)   rel")
 worst = {"u": 0.0, "p": 0.0, "dt": 0.0, "f": 0.0, "nmis": 0}

@@ -169,7 +169,7 @@ def mailbox_timeout(rank, size):
     v = (C.c_double * 1)(float(rank + 1))
     _lib.check(Lb.wl_allreduce(v, 1, 0))                       # a healthy round first
     ok_sum = v[0] == sum(range(1, size + 1))
-    S.set_option(26, 1)                                        # one second of the device's wall clock
+    S.set_option(S.Opt.MBOX_TIMEOUT_S, 1)                      # one second of the device's wall clock
     raised, msg = False, ""
     if rank == 0:
         try:

@@ -142,7 +142,7 @@ def test_projection_divergence_free_and_uniform_stream(S, flow, case):
 
 
 def test_rows_per_thread_same_bits(S, flow):
-    """wl_set_option(4): the 7-point kernel with one or two rows per thread evaluates the same per-cell expressions:
+    """Opt.STENCIL7_ROWS: the 7-point kernel with one or two rows per thread evaluates the same per-cell expressions:
     mult!, Jacobi!+increment! and the fused V-cycle smoother give bit-identical fields at full size."""
     a, ml, U = flow
     lv = ml.levels[0]
@@ -153,15 +153,12 @@ def test_rows_per_thread_same_bits(S, flow):
     r0[inner] = rand_like(r0[inner], 12)
     out = []
     for rows in (1, 2):
-        S.set_option(4, rows)
-        try:
+        with S.options({S.Opt.STENCIL7_ROWS: rows}):
             z = S.copy_of(S.mult(ml, x))
             lv.r.copy_(r0)
             a.p.zero_()
             S.Jacobi(ml)                                      # eps = r*iD ; r -= A eps ; x += eps
             out.append((z, S.copy_of(lv.r), S.copy_of(a.p)))
-        finally:
-            S.set_option(4, 0)
     for u, v in zip(*out):
         assert torch.equal(u, v)
 
@@ -173,35 +170,34 @@ def _bench_case(dims, T, kind):
 
 def test_traffic_saving_switches_do_not_change_a_bit(S, case):
     """The kernels that move fewer bytes than the dense algorithm -- row constants instead of L/iD in coefficient-
-    uniform rows (option 9), x += alpha*eps deferred to the direction kernel (8), z' = r*iD recomputed instead of
-    stored (13), z = A*eps formed a second time by the update kernel instead of stored (19), body-free rows in BDIM! (3), the chained x/=dt ; x*=dt' pass (14), the shared-flux conv_diff! kernel (18), div(u)
-    formed inside residual! (22), the x planes of BC! written by the producing kernel (23), consecutive kernels sweeping in
-    opposite directions (30) -- evaluate the same expressions: three steps of the case give
+    uniform rows (ROW_CONST_L), x += alpha*eps deferred to the direction kernel (PCG_DEFER_X), z' = r*iD recomputed instead of
+    stored (PCG_RECOMPUTE_PRECOND), z = A*eps formed a second time by the update kernel instead of stored (PCG_RECOMPUTE_AEPS),
+    body-free rows in BDIM! (BDIM_ROWFLAGS), the chained x/=dt ; x*=dt' pass (SCALE_CHAIN), the shared-flux conv_diff! kernel
+    (CONVDIFF_SHARED_FLUX), div(u) formed inside residual! (DIV_IN_RESIDUAL), the x planes of BC! written by the producing
+    kernel (XGHOST_IN_KERNEL), consecutive kernels sweeping in opposite directions (SWEEP_ALTERNATE) -- evaluate the same expressions: three steps of the case give
     bit-identical u and p with all of them off."""
     dims, T, kind = case
     if int(np.prod(dims)) > 512 ** 3:
         pytest.skip("C4: the same kernels at four times the cells (55 s); C2, C3 and C5 run this comparison")
-    # Float64: options 8, 13 and 19 decide which kernels accumulate pcg!'s dot products and how their grids are cut (the
-    # in-kernel finalisation needs 8 and 13; 19 moves r.z' into a 7-point kernel): the SAME terms are summed in a different
+    # Float64: PCG_DEFER_X, PCG_RECOMPUTE_PRECOND and PCG_RECOMPUTE_AEPS decide which kernels accumulate pcg!'s dot products and
+    # how their grids are cut (the in-kernel finalisation needs the first two; the third moves r.z' into a 7-point kernel): the SAME terms are summed in a different
     # grouping.  Rounded to Float32 the sums are the same numbers; in Float64 their last bits differ, and with them
     # everything downstream (tools/whichswitch.py) -- so there these three are compared on their own, to rounding, and the
     # other switches (none of which regroups a sum) bit for bit.
     f64 = np.dtype(T) == np.float64
-    keys = (3, 9, 14, 18, 22, 23, 30) + (() if f64 else (8, 13, 19))
-    regroup = (8, 13, 19)
+    Opt = S.Opt
+    regroup = (Opt.PCG_DEFER_X, Opt.PCG_RECOMPUTE_PRECOND, Opt.PCG_RECOMPUTE_AEPS)
+    keys = (Opt.BDIM_ROWFLAGS, Opt.ROW_CONST_L, Opt.SCALE_CHAIN, Opt.CONVDIFF_SHARED_FLUX, Opt.DIV_IN_RESIDUAL, Opt.XGHOST_IN_KERNEL,
+            Opt.SWEEP_ALTERNATE) + (() if f64 else regroup)
 
     def run(off):
-        for key in off:
-            S.set_option(key, 0)
-        if 19 not in off and not f64:
-            S.set_option(19, 2)                       # (2 = on every level, also the finest one)
-        try:
+        values = {key: 0 for key in off}
+        if Opt.PCG_RECOMPUTE_AEPS not in off and not f64:
+            values[Opt.PCG_RECOMPUTE_AEPS] = 2        # (2 = on every level, also the finest one)
+        with S.options(values):
             sim = _bench_case(dims, T, kind)
             for _ in range(3):
                 S.sim_step(sim, remeasure=False)
-        finally:
-            for key in keys + regroup:
-                S.set_option(key, 1)
         nu, nr = S.uniform_rows(sim.pois, 0)
         out = (sim.pois.n[:], list(sim.flow.dt), S.copy_of(sim.flow.u), S.copy_of(sim.flow.p), nu, nr)
         del sim                                       # one simulation at a time (C4: 68 GB each)

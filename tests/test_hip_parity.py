@@ -22,6 +22,7 @@ import bodies
 from oracle import geometry as G
 from oracle import wl_oracle as O
 from waterlily_amd import sim as S
+from waterlily_amd.sim import Opt
 
 TYPES = [np.float32, np.float64]
 SHAPES = [(18, 12), (12, 10, 8)]
@@ -106,10 +107,9 @@ def test_conv_diff_bit_exact(T, Ng, perdir):
 def test_conv_diff_tile_paths_bit_exact(T, Ng, shared):
     """The LDS conv_diff kernels on shapes that exercise every tile kind: several x tiles per row (first / last with the
     domain's x-boundary faces, plain ones in between), partially filled last tiles, first / last tile rows and boundary
-    planes (the per-cell-gather kernel) around the interior block (the shared-flux kernel, wl_set_option(18)): bit-exact
+    planes (the per-cell-gather kernel) around the interior block (the shared-flux kernel, Opt.CONVDIFF_SHARED_FLUX): bit-exact
     against the oracle either way."""
-    S.set_option(18, 1 if shared else 0)                 # (Float32 runs 64x8 + 64x4 tiles, Float64 64x4: both tile kernels are covered)
-    try:
+    with S.options({Opt.CONVDIFF_SHARED_FLUX: 1 if shared else 0}):   # (Float32 runs 64x8 + 64x4 tiles, Float64 64x4: both tile kernels are covered)
         u = rnd(Ng + (3,), T, 8)
         r, Phi = O.zeros(Ng + (3,), T), O.zeros(Ng, T)
         O.conv_diff(r, u, Phi, nu=0.03)
@@ -120,8 +120,6 @@ def test_conv_diff_tile_paths_bit_exact(T, Ng, shared):
         shell = np.ones(Ng, bool)
         shell[O.inside(Phi)] = False
         assert np.array_equal(S.to_host(Pd)[shell], Phi[shell])          # the flux scratch left in Phi's ghost cells
-    finally:
-        S.set_option(18, 1)
 
 
 @pytest.mark.parametrize("T", TYPES)
@@ -178,16 +176,21 @@ def lev_h(ph):
     return ph.levels[0]
 
 
+@pytest.fixture
+def rows_option(request):
+    """Opt.STENCIL7_ROWS = the test's `rows` parameter while the test runs"""
+    with S.options({Opt.STENCIL7_ROWS: request.node.callspec.params["rows"]}):
+        yield
+
+
 @pytest.mark.parametrize("T", TYPES)
 @pytest.mark.parametrize("Ng", [(18, 18), (18, 18, 18)])
 @pytest.mark.parametrize("padded", [True, False])
 @pytest.mark.parametrize("rows", [0, 2])
-def test_poisson_operators(T, Ng, padded, rows, request):
-    """rows: wl_set_option(4): 0 = default tiling of the 7-point kernel, 2 = two rows per thread forced (3-D only)"""
+def test_poisson_operators(T, Ng, padded, rows, rows_option):
+    """rows: Opt.STENCIL7_ROWS: 0 = default tiling of the 7-point kernel, 2 = two rows per thread forced (3-D only)"""
     if rows and len(Ng) == 2:
         pytest.skip("rows per thread only exists in the 3-D vector kernel")
-    S.set_option(4, rows)
-    request.addfinalizer(lambda: S.set_option(4, 0))
     po, ph = make_pois(Ng, T, O.MultiLevelPoisson, S.MultiLevelPoisson, padded=padded)
     assert len(po.levels) == len(ph.levels)
     for lo, lh in zip(po.levels, ph.levels):            # set_diag!, restrictL!: bit-exact on every level
@@ -230,11 +233,9 @@ def test_poisson_operators(T, Ng, padded, rows, request):
 @pytest.mark.parametrize("T", TYPES)
 @pytest.mark.parametrize("Ng", [(34, 18), (18, 18, 10), (34, 34, 18)])
 @pytest.mark.parametrize("rows", [0, 2])
-def test_pcg_vcycle_solver(T, Ng, rows, request):
+def test_pcg_vcycle_solver(T, Ng, rows, rows_option):
     if rows and len(Ng) == 2:
         pytest.skip("rows per thread only exists in the 3-D vector kernel")
-    S.set_option(4, rows)
-    request.addfinalizer(lambda: S.set_option(4, 0))
     po, ph = make_pois(Ng, T, O.MultiLevelPoisson, S.MultiLevelPoisson)
     z0 = po.z.copy(order="F")
     O.residual(po)
@@ -262,7 +263,7 @@ def test_pcg_vcycle_solver(T, Ng, rows, request):
 @pytest.mark.parametrize("xdefer", [1, 0])
 def test_pcg_exit_right_after_update(T, padded, xdefer):
     """pcg! leaving through Poisson.jl:138 (|rho2| < 10eps straight after an update).  The x update of that iteration
-    still has to land: the default kernels apply it in the direction kernel (wl_set_option(8)), which must run for
+    still has to land: the default kernels apply it in the direction kernel (Opt.PCG_DEFER_X), which must run for
     exactly that owed update and nothing else.  Fully periodic unit-coefficient system, plane-wave residual: the
     Jacobi-preconditioned direction is an eigenvector, so one iteration solves it."""
     Ng, D = (18, 18, 18), 3
@@ -278,11 +279,8 @@ def test_pcg_exit_right_after_update(T, padded, xdefer):
     ph = S.Poisson(field(x, D, padded), field(L, D, padded), field(z, D, padded), perdir=perdir)
     po.r[...] = r
     S.upload(lev_h(ph).r, r)
-    S.set_option(8, xdefer)
-    try:
+    with S.options({Opt.PCG_DEFER_X: xdefer}):
         n_o, n_h = O.pcg(po), S.pcg(ph)
-    finally:
-        S.set_option(8, 1)
     assert n_o == n_h == 1                              # one (x,r) update, then the :138 return
     ins = O.inside(x)
     assert np.abs(po.x[ins] - x[ins]).max() > 0.1       # and x really moved
@@ -307,7 +305,7 @@ def _blob_system(T, cls_o, cls_h, padded=True):
 
 @pytest.mark.parametrize("T", TYPES)
 def test_uniform_rows_are_skipped_exactly(T):
-    """wl_set_option(9): rows whose face coefficients are all one number use that number instead of loading L.
+    """Opt.ROW_CONST_L: rows whose face coefficients are all one number use that number instead of loading L.
     Same values => every operator is bit-identical with the switch on and off, and mult! stays bit-exact
     against the oracle on every level (c = 1, 2, 4 ... down the hierarchy)."""
     po, ph, x = _blob_system(T, O.MultiLevelPoisson, S.MultiLevelPoisson)
@@ -325,13 +323,10 @@ def test_uniform_rows_are_skipped_exactly(T):
     same(ph.z, po.z)
     # the whole solver, switch on vs off, on twin systems
     _, ph0, _ = _blob_system(T, O.MultiLevelPoisson, S.MultiLevelPoisson)
-    S.set_option(9, 0)
-    try:
+    with S.options({Opt.ROW_CONST_L: 0}):
         S.mult(ph0, field(x, 3, True))                   # same source term z = A x as the twin above
         assert np.array_equal(S.to_host(ph0.z), S.to_host(ph.z))
         S.solver(ph0)
-    finally:
-        S.set_option(9, 1)
     S.solver(ph)
     O.solver(po)
     assert ph.n == ph0.n == po.n
@@ -343,7 +338,7 @@ def test_uniform_rows_are_skipped_exactly(T):
 @pytest.mark.parametrize("T", TYPES)
 @pytest.mark.parametrize("dims", [(64, 32), (192, 64), (32, 32, 32), (64, 48, 16)])
 def test_coarse_tail_on_chip_bit_exact(T, dims):
-    """wl_set_option(31): inside the one-workgroup bottom of the V-cycle pcg! keeps its level in registers + LDS instead of
+    """Opt.COARSE_PCG_RESIDENT: inside the one-workgroup bottom of the V-cycle pcg! keeps its level in registers + LDS instead of
     going through global memory between its phases.  Same expressions, same order of every sum: every field after several
     steps (and every coarse level's x, r, eps, z after a V-cycle) is bit-identical with the switch on and off; levels of
     1 and of 4 cells per thread, 2-D and 3-D."""
@@ -352,14 +347,11 @@ def test_coarse_tail_on_chip_bit_exact(T, dims):
     ubc = (1.0,) + (0.0,) * (len(dims) - 1)
     runs = []
     for on in (1, 0):
-        S.set_option(31, on)
-        try:
+        with S.options({Opt.COARSE_PCG_RESIDENT: on}):
             from waterlily_amd import body as B
             s = S.Simulation(dims, ubc, 2 * R, nu=2 * R / 250, body=B.Sphere(c, R, len(dims)), T=T)
             for _ in range(4):
                 S.sim_step(s, remeasure=False)
-        finally:
-            S.set_option(31, 1)
         runs.append(s)
     a, b = runs
     assert a.pois.n == b.pois.n
@@ -371,17 +363,14 @@ def test_coarse_tail_on_chip_bit_exact(T, dims):
 
 @pytest.mark.parametrize("T", TYPES)
 def test_pcg_without_stored_z_bit_exact(T):
-    """wl_set_option(19): pcg!'s update kernel forms z = A*eps a second time (7-point kernel over eps) instead of reading
+    """Opt.PCG_RECOMPUTE_AEPS: pcg!'s update kernel forms z = A*eps a second time (7-point kernel over eps) instead of reading
     the z the mult kernel stored.  Same expression on the same operands => x and r after the whole solver are
     bit-identical to the run that stores z; both match the oracle."""
     res = []
     for on in (2, 0):
-        S.set_option(19, on)
-        try:
+        with S.options({Opt.PCG_RECOMPUTE_AEPS: on}):
             po, ph, _ = _blob_system(T, O.MultiLevelPoisson, S.MultiLevelPoisson)
             S.solver(ph)
-        finally:
-            S.set_option(19, 1)
         res.append(ph)
     O.solver(po)
     assert res[0].n == res[1].n == po.n
@@ -393,14 +382,11 @@ def test_pcg_without_stored_z_bit_exact(T):
 @pytest.mark.parametrize("T", TYPES)
 @pytest.mark.parametrize("rows", [1, 2])
 def test_rows_per_thread_variants(T, rows):
-    """wl_set_option(4, R): the 7-point kernel with R = 1 or 2 rows per thread (the default picks by level size).  Same
+    """Opt.STENCIL7_ROWS = R: the 7-point kernel with R = 1 or 2 rows per thread (the default picks by level size).  Same
     per-cell expressions => same bits as the default form, on a system with coefficient-uniform rows and body rows."""
-    S.set_option(4, rows)
-    try:
+    with S.options({Opt.STENCIL7_ROWS: rows}):
         _, ph1, x = _blob_system(T, O.MultiLevelPoisson, S.MultiLevelPoisson)
         S.solver(ph1)
-    finally:
-        S.set_option(4, 0)
     po, ph2, _ = _blob_system(T, O.MultiLevelPoisson, S.MultiLevelPoisson)
     S.solver(ph2)
     O.solver(po)
@@ -477,21 +463,18 @@ def test_mom_step_3d_sphere(T):
 
 @pytest.mark.parametrize("T", TYPES)
 def test_project_div_inside_residual_bit_exact(T):
-    """wl_set_option(22): inside mom_step! the right-hand side z = div(u) of project! is formed by the residual! kernel
+    """Opt.DIV_IN_RESIDUAL: inside mom_step! the right-hand side z = div(u) of project! is formed by the residual! kernel
     itself (no z array pass).  Same differences in the same order => every field after several steps is bit-identical
     to the run with the separate div pass, which in turn matches the oracle."""
     m = 48
     R, c = m / 8, m / 2 - 1
     runs = []
     for fused in (1, 0):
-        S.set_option(22, fused)
-        try:
+        with S.options({Opt.DIV_IN_RESIDUAL: fused}):
             so, sh = pair((m, m, m), (1.0, 0.0, 0.0), 2 * R, nu=2 * R / 3700, body=bodies.sphere(c, R), T=T)
             for _ in range(3):
                 S.sim_step(sh, remeasure=False)
             runs.append((sh.pois.n[:], S.to_host(sh.flow.u).copy(), S.to_host(sh.flow.p).copy(), list(sh.flow.dt)))
-        finally:
-            S.set_option(22, 1)
     assert runs[0][0] == runs[1][0]
     assert np.array_equal(runs[0][1], runs[1][1]) and np.array_equal(runs[0][2], runs[1][2])
     assert runs[0][3] == runs[1][3]
@@ -504,7 +487,7 @@ def test_project_div_inside_residual_bit_exact(T):
 @pytest.mark.parametrize("T", TYPES)
 @pytest.mark.parametrize("case", ["sphere", "sphere-on-the-wall", "moving", "gravity", "dense"])
 def test_bdim_finished_inside_conv_diff_bit_exact(T, case):
-    """wl_set_option(27): inside mom_step! the conv_diff! kernels finish BDIM! (Flow.jl:134, scale_u! :166) on the body-free
+    """Opt.BDIM_IN_CONVDIFF: inside mom_step! the conv_diff! kernels finish BDIM! (Flow.jl:134, scale_u! :166) on the body-free
     x-rows themselves -- the new velocity of such a row is stored from the registers that hold f, V is not read there, the
     row's x-ghost cells of the following BC! are written too -- and the two velocity arrays take turns (the predictor writes
     u' into the u0 array, the corrector the new velocity back into u), the busy rows keep their own kernel.  Same expressions
@@ -526,8 +509,7 @@ def test_bdim_finished_inside_conv_diff_bit_exact(T, case):
         kw["padded"] = False
     runs = []
     for fused in (1, 0):
-        S.set_option(27, fused)
-        try:
+        with S.options({Opt.BDIM_IN_CONVDIFF: fused}):
             so, sh = pair(dims, (1.0, 0.0, 0.0), 2 * R, nu=2 * R / 1000, body=body, **kw)
             u_start = S.to_host(sh.flow.u).copy()
             for _ in range(3):
@@ -535,8 +517,6 @@ def test_bdim_finished_inside_conv_diff_bit_exact(T, case):
                 S.sim_step(sh, remeasure=(case == "moving"))
             runs.append((sh.pois.n[:], list(sh.flow.dt), S.to_host(sh.flow.u).copy(), S.to_host(sh.flow.p).copy(), S.to_host(sh.flow.f).copy(),
                          S.to_host(sh.flow.u0).copy(), u_before))
-        finally:
-            S.set_option(27, 1)
     a, b = runs
     assert a[0] == b[0] and a[1] == b[1]
     for q in (2, 3, 4):
@@ -553,7 +533,7 @@ def test_bdim_finished_inside_conv_diff_bit_exact(T, case):
 @pytest.mark.parametrize("T", TYPES)
 @pytest.mark.parametrize("exitBC", [False, True])
 def test_x_ghost_cells_written_by_the_producer_bit_exact(T, exitBC):
-    """wl_set_option(23): inside mom_step! the x-ghost cells of the interior rows that BC!(u,U) sets are written by the
+    """Opt.XGHOST_IN_KERNEL: inside mom_step! the x-ghost cells of the interior rows that BC!(u,U) sets are written by the
     kernel that produces the row (BDIM!, the velocity correction), the BC launch covers the y / z planes only.  Every
     element of u -- ghost cells included -- after several steps is bit-identical to the run whose BC! writes all six
     planes, and matches the oracle."""
@@ -561,14 +541,11 @@ def test_x_ghost_cells_written_by_the_producer_bit_exact(T, exitBC):
     R, c = dims[1] / 8, dims[1] / 2 - 1
     runs = []
     for fold in (1, 0):
-        S.set_option(23, fold)
-        try:
+        with S.options({Opt.XGHOST_IN_KERNEL: fold}):
             so, sh = pair(dims, (1.0, 0.0, 0.0), 2 * R, nu=2 * R / 1000, body=bodies.sphere(c, R), T=T, exitBC=exitBC)
             for _ in range(3):
                 S.sim_step(sh, remeasure=False)
             runs.append((sh.pois.n[:], S.to_host(sh.flow.u).copy(), S.to_host(sh.flow.p).copy(), list(sh.flow.dt)))
-        finally:
-            S.set_option(23, 1)
     assert runs[0][0] == runs[1][0] and runs[0][3] == runs[1][3]
     assert np.array_equal(runs[0][1], runs[1][1]) and np.array_equal(runs[0][2], runs[1][2])
     for _ in range(3):
@@ -660,7 +637,11 @@ def test_bench_moving_cylinder_case_against_the_oracle(T):
     same(sh.flow.p, so.flow.p, exact=False, tol=rtol(T) * 500)
 
 
-SWITCHES = {0: 0, 1: 0, 2: 0, 3: 0, 5: 0, 6: 0, 7: 0, 8: 0, 9: 0, 10: 0, 13: 0, 14: 0, 15: 0, 18: 0, 19: 0, 22: 0, 23: 0, 27: 0, 30: 0, 31: 0}
+SWITCHES = {k: 0 for k in (
+    Opt.STENCIL7_VEC, Opt.SMOOTH_FUSED, Opt.CONVDIFF_TILED, Opt.BDIM_ROWFLAGS, Opt.PCG_VEC, Opt.COARSE_TAIL, Opt.BC_FUSED,
+    Opt.PCG_DEFER_X, Opt.ROW_CONST_L, Opt.PCG_START_FUSED, Opt.PCG_RECOMPUTE_PRECOND, Opt.SCALE_CHAIN, Opt.PCG_DOTS_IN_KERNEL,
+    Opt.CONVDIFF_SHARED_FLUX, Opt.PCG_RECOMPUTE_AEPS, Opt.DIV_IN_RESIDUAL, Opt.XGHOST_IN_KERNEL, Opt.BDIM_IN_CONVDIFF,
+    Opt.SWEEP_ALTERNATE, Opt.COARSE_PCG_RESIDENT)}
 
 
 @pytest.mark.parametrize("group", ["all-at-once", "vector-kernels-kept", "two-rows-and-no-finalize-launches", "x-planes-by-the-BC-launch"])
@@ -682,20 +663,15 @@ def test_every_switch_flipped_at_once_changes_no_bit(group):
     base = run()
     flips = dict(SWITCHES)
     if group == "vector-kernels-kept":
-        for k in (0, 2, 5):
+        for k in (Opt.STENCIL7_VEC, Opt.CONVDIFF_TILED, Opt.PCG_VEC):
             flips.pop(k)
     elif group == "two-rows-and-no-finalize-launches":
-        flips = {4: 2, 15: 2, 19: 2, 30: 0, 3: 0, 9: 0}
+        flips = {Opt.STENCIL7_ROWS: 2, Opt.PCG_DOTS_IN_KERNEL: 2, Opt.PCG_RECOMPUTE_AEPS: 2, Opt.SWEEP_ALTERNATE: 0, Opt.BDIM_ROWFLAGS: 0,
+                 Opt.ROW_CONST_L: 0}
     elif group == "x-planes-by-the-BC-launch":       # BDIM! still finished inside conv_diff!, the x-ghost cells by BC!'s own launch
-        flips = {23: 0}
-    keep = {k: S.get_option(k) for k in flips}
-    try:
-        for k, v in flips.items():
-            S.set_option(k, v)
+        flips = {Opt.XGHOST_IN_KERNEL: 0}
+    with S.options(flips):
         other = run()
-    finally:
-        for k, v in keep.items():
-            S.set_option(k, v)
     assert base.pois.n == other.pois.n and base.flow.dt == other.flow.dt
     assert torch.equal(base.flow.u, other.flow.u) and torch.equal(base.flow.p, other.flow.p)
     assert torch.equal(base.flow.f, other.flow.f)
@@ -1285,16 +1261,13 @@ def test_native_measure_matches_oracle(T):
         S.sim_step(sh)
     assert so.pois.n == sh.pois.n and sh.pois.n[:2] == [2, 1]
     same(sh.flow.u, so.flow.u, exact=False, tol=50 * rtol(T))
-    # the body-free row flags the native path derives from its touched rows: BDIM! with them == BDIM! without (option 3)
+    # the body-free row flags the native path derives from its touched rows: BDIM! with them == BDIM! without (Opt.BDIM_ROWFLAGS)
     runs = []
     for on in (1, 0):
-        S.set_option(3, on)
-        try:
+        with S.options({Opt.BDIM_ROWFLAGS: on}):
             s3 = S.Simulation((m, m, m), (1.0, 0.0, 0.0), 8.0, body=bodies.moving_circle(12.0, 4.0, v=1.0, D=3).native(3), nu=0.05, T=T)
             for _ in range(3):
                 S.sim_step(s3)
-        finally:
-            S.set_option(3, 1)
         runs.append(s3)
     assert runs[0].pois.n == runs[1].pois.n
     assert torch.equal(runs[0].flow.u, runs[1].flow.u) and torch.equal(runs[0].flow.p, runs[1].flow.p)

@@ -210,7 +210,7 @@ def test_allreduce_latency_is_reported(nproc, mailbox):
 
 @pytest.mark.gpu
 def test_mailbox_allreduce_gives_up_on_a_missing_peer():
-    """the waits of the mailbox all-reduce are bounded (wl_set_option(26)): a healthy round sums correctly; when a peer never
+    """the waits of the mailbox all-reduce are bounded (Opt.MBOX_TIMEOUT_S): a healthy round sums correctly; when a peer never
     posts, the waiting rank's kernel ends, and the library turns the flag into an error at its next synchronisation"""
     out = run_workers("mg_worker.py", 2, "mboxtimeout_f32", timeout=120)
     assert out["ok_sum"] and out["raised"] and "mailbox" in out["msg"], out

@@ -1,6 +1,6 @@
 """The kernels that only run inside a whole step or a whole V-cycle, against the extended-precision reference tests/xref.py
 (the operators one by one are in test_xref_gpu.py):
-- the fused conv_diff!+BDIM! kernels of mom_step! (wl_set_option(27)): the corrector's f after one step (xref.mom_f) at
+- the fused conv_diff!+BDIM! kernels of mom_step! (Opt.BDIM_IN_CONVDIFF): the corrector's f after one step (xref.mom_f) at
   the 64-cell x tile seams, odd and even numbers of interior tile rows of the 8-row (Float32) and 4-row tiles, the
   smallest z extents the tiled kernel takes; and the fused step bit-identical to the separate BDIM! pass there;
 - the one-workgroup bottom of the V-cycle (wl_coarse.h): tail on against the per-level launches, the invariant
@@ -17,6 +17,7 @@ pytestmark = pytest.mark.gpu
 import xref as X
 from oracle import wl_oracle as O
 from waterlily_amd import sim as S
+from waterlily_amd.sim import Opt
 from xref_inputs import coefficients, field, periodic_subsets, step_fields
 from test_xref_gpu import WORST, check, dev, fails     # one record of worst ratios for both GPU xref files
 
@@ -27,13 +28,13 @@ K = X.K
 # ----------------------------------------------------------------------------- mom_step!: fused conv_diff!+BDIM!
 
 def fused_mom_step(a: S.Flow, row_flags_built: bool) -> bool:
-    """wl_api.hip flow_mom_step: `turns` = options 27 and 3 && a->rowfree && a->busy && no periodic direction && no
-    convective exit && conv_diff_tiled(g, 0) (wl_ops.h: D == 3, option 2, every extent >= 5).  a->rowfree and a->busy are
+    """wl_api.hip flow_mom_step: `turns` = BDIM_IN_CONVDIFF and BDIM_ROWFLAGS && a->rowfree && a->busy && no periodic direction && no
+    convective exit && conv_diff_tiled(g, 0) (wl_ops.h: D == 3, CONVDIFF_TILED, every extent >= 5).  a->rowfree and a->busy are
     not visible from the host: both are set by flow_compact_busy, which every wl_flow_update runs (the busy list is
     allocated even when empty), so the caller passes whether wl_flow_update ran on this flow.  The tests also check the
     observable the fused path leaves: the u0 array holds u', not the copy of u_start (wl_mom_step)."""
-    return (a.D == 3 and S.get_option(27) != 0 and S.get_option(3) != 0 and row_flags_built and not a.perdir
-            and not a.exitBC and S.get_option(2) != 0 and all(n >= 5 for n in a.N))
+    return (a.D == 3 and S.get_option(Opt.BDIM_IN_CONVDIFF) != 0 and S.get_option(Opt.BDIM_ROWFLAGS) != 0 and row_flags_built
+            and not a.perdir and not a.exitBC and S.get_option(Opt.CONVDIFF_TILED) != 0 and all(n >= 5 for n in a.N))
 
 
 def cd_tiles(Ng, T):
@@ -47,7 +48,7 @@ def cd_tiles(Ng, T):
     odd = use8 and (thi - tlo + 1) % 2 == 1 and thi > tlo
     if odd:
         thi -= 1                                           # 8-row tiles: an odd tile row goes to the shell
-    assert S.get_option(18) != 0 and thi >= tlo and khi >= klo, "the shared-flux kernel must run"
+    assert S.get_option(Opt.CONVDIFF_SHARED_FLUX) != 0 and thi >= tlo and khi >= klo, "the shared-flux kernel must run"
     rows = (thi - tlo + 1) * 4
     n8 = rows // 8 if use8 else 0
     return dict(ntx=ntx, n8=n8, n4=(rows - 8 * n8) // 4, shell_rows=nty_all - (thi + 1), planes=khi - klo + 1,
@@ -127,21 +128,18 @@ def test_mom_step_fused_f_hip_vs_xref(T):
 
 @pytest.mark.parametrize("T", TYPES)
 def test_mom_step_fused_bit_exact_at_tile_edges(T):
-    """At the shapes above, three steps with option 27 on and off: u (ghost cells included), p, f, dt and the V-cycle
+    """At the shapes above, three steps with Opt.BDIM_IN_CONVDIFF on and off: u (ghost cells included), p, f, dt and the V-cycle
     counts bit-identical; the u0 array holds u' (fused) or u_start (separate)."""
     for q, dims in enumerate(step_cases(T)):
         runs = []
         for on in (1, 0):
-            S.set_option(27, on)
-            try:
+            with S.options({Opt.BDIM_IN_CONVDIFF: on}):
                 a, b, Ng = make_step(dims, T, q % 2 == 1, 900 + q)
                 assert fused_mom_step(a, row_flags_built=True) == bool(on)
                 for _ in range(3):
                     u_before = S.to_host(a.u).copy()
                     S.mom_step(a, b)
                 runs.append((b.n[:], list(a.dt), S.to_host(a.u), S.to_host(a.p), S.to_host(a.f), S.to_host(a.u0), u_before))
-            finally:
-                S.set_option(27, 1)
         x, y = runs
         assert x[0] == y[0] and x[1] == y[1], dims
         for k in (2, 3, 4):
@@ -164,7 +162,7 @@ def tail_plan(shapes, l, opt6):
     pcg! form k_coarse_vcycle takes: 'lds1' / 'lds4' (cv_pcg_onchip with 1 / CV_CPT cells per thread, where cv_fits_lds
     holds) or 'global' (cv_pcg)"""
     thr = CV_MAXCELLS if opt6 == 1 else opt6
-    assert S.get_option(1) != 0
+    assert S.get_option(Opt.SMOOTH_FUSED) != 0
     for c in range(l + 1, len(shapes)):
         if opt6 and interior(shapes[c]) <= thr and len(shapes) - c <= CV_MAXLEV:
             kinds = []
@@ -175,7 +173,7 @@ def tail_plan(shapes, l, opt6):
     return None, []
 
 
-# (interior dims, option 6, level the tail must start on, pcg! form of that level)
+# (interior dims, Opt.COARSE_TAIL, level the tail must start on, pcg! form of that level)
 TAIL_CASES = [
     ((32, 32, 32), 1, 1, "lds4"),        # exactly 4096 cells: 16^3
     ((128, 128), 1, 1, "lds4"),          # 64^2
@@ -183,7 +181,7 @@ TAIL_CASES = [
     ((64, 32), 1, 1, "lds1"),
     ((512, 8, 8), 1, 1, "global"),       # 256x4x4 = 4096 cells, 258*6*6 = 9288 elements > CV_LDS: cv_pcg inside the launch
     ((32, 32, 36), 1, 2, "lds1"),        # 16x16x18 = 4608 cells just above: per-level launches, the tail one level lower
-    ((64, 64, 64), 32768, 1, "global"),  # option 6 forced: 32^3 cells in the tail
+    ((64, 64, 64), 32768, 1, "global"),  # COARSE_TAIL forced: 32^3 cells in the tail
     ((256, 128), 8192, 1, "global"),     # 128x64 = 8192
 ]
 
@@ -212,7 +210,7 @@ def invariant_ratio(h1, rhs, rhsM, T):
 @pytest.mark.parametrize("T", TYPES)
 @pytest.mark.parametrize("case", TAIL_CASES, ids=lambda c: "x".join(map(str, c[0])) + f"-opt6={c[1]}")
 def test_coarse_tail_hip_vs_per_level_and_xref(T, case):
-    """One Vcycle!(ml, 0) with the tail (option 6 as given) against the same V-cycle in per-level launches (option 6 = 0):
+    """One Vcycle!(ml, 0) with the tail (Opt.COARSE_TAIL as given) against the same V-cycle in per-level launches (COARSE_TAIL = 0):
     pcg! leaves every coarse level by the same exit, and x, r, eps, z agree within K = coarse_tail times eps_T and the
     level's scale of that array (the per-cell arithmetic is the same, the Float64 dot sums group differently: pcg!'s alpha
     and beta can round apart by an ulp of T, and the levels above inherit that through prolongate!); control: level 1's
@@ -237,13 +235,9 @@ def test_coarse_tail_hip_vs_per_level_and_xref(T, case):
     for o in (opt6, 0):
         _, _, p = tail_system(dims, T, seed)
         S.residual(p)
-        S.set_option(6, o)
-        S.set_option(13, 1 if o else 0)      # per-level pcg! stores z' = r*iD, as the reference and the tail do
-        try:
+        # (per-level pcg! stores z' = r*iD, as the reference and the tail do)
+        with S.options({Opt.COARSE_TAIL: o, Opt.PCG_RECOMPUTE_PRECOND: 1 if o else 0}):
             S.Vcycle(p, 0)
-        finally:
-            S.set_option(6, 1)
-            S.set_option(13, 1)
         got[o] = [level_host(p, l) for l in range(len(shapes))]
     on, off = got[opt6], got[0]
     for l in range(1, len(shapes)):
@@ -275,11 +269,8 @@ def test_coarse_tail_hip_vs_per_level_and_xref(T, case):
     L1 = p.levels[1].L
     I = tuple(n // 2 for n in shapes[1])
     L1[I + (0,)] *= 1.25
-    S.set_option(6, opt6)
-    try:
+    with S.options({Opt.COARSE_TAIL: opt6}):
         S.Vcycle(p, 0)
-    finally:
-        S.set_option(6, 1)
     hp = level_host(p, 1)
     hp["L"], hp["D"] = on[1]["L"], on[1]["D"]
     assert invariant_ratio(hp, rhs, rhsM, T) > K["coarse_inv"]
@@ -287,11 +278,8 @@ def test_coarse_tail_hip_vs_per_level_and_xref(T, case):
     xh = np.zeros(Ng, T, order="F")
     po = O.MultiLevelPoisson(xh.copy(order="F"), L.copy(order="F"), z.copy(order="F"))
     _, _, p = tail_system(dims, T, seed)
-    S.set_option(6, opt6)
-    try:
+    with S.options({Opt.COARSE_TAIL: opt6}):
         S.solver(p)
-    finally:
-        S.set_option(6, 1)
     O.solver(po)
     assert p.n == po.n
     rt = 1e-5 if np.dtype(T) == np.float32 else 1e-12

@@ -1,12 +1,12 @@
 #!/usr/bin/env python3
-"""In-process A/B of whole sim_step! time for one wl_set_option key.  usage: ab_step.py <size> <key> [reps [valA valB]]
+"""In-process A/B of whole sim_step! time for one wl_set_option key.  usage: ab_step.py <size> <key> [reps [valA valB]]   (e.g. ab_step.py 256 BDIM_IN_CONVDIFF; a key is a name or a number: BDIM_IN_CONVDIFF or 27)
 (WL_AB_DTYPE=f64: Float64; WL_AB_LAYOUT=dense: the reference's strides)"""
 import os, sys, time
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench
 from waterlily_amd import _lib, sim as S
-size, key = int(sys.argv[1]), int(sys.argv[2])
+size, key = int(sys.argv[1]), S.opt_key(sys.argv[2])
 reps = int(sys.argv[3]) if len(sys.argv) > 3 else 4
 vals = (int(sys.argv[4]), int(sys.argv[5])) if len(sys.argv) > 5 else (1, 0)
 L = _lib.lib()
@@ -25,4 +25,4 @@ for r in range(reps):
         torch.cuda.synchronize()
         res[val].append((time.perf_counter() - t0) / 5 * 1e3)
 for val in vals:
-    print(f"{size}^3 option[{key}]={val}: median {np.median(res[val]):.3f} ms/step  (all: {[round(x, 2) for x in res[val]]})  n={sim.pois.n[-2:]}")
+    print(f"{size}^3 {S.opt_name(key)} = {val}: median {np.median(res[val]):.3f} ms/step  (all: {[round(x, 2) for x in res[val]]})  n={sim.pois.n[-2:]}")

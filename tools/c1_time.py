@@ -15,12 +15,12 @@ for dims, T, Re in (((192, 64), np.float64, 100.0), ((768, 256), np.float32, 100
     for _ in range(K):
         S.sim_step(s, remeasure=False)
     torch.cuda.synchronize(); dt = (time.perf_counter() - t0) / K
-    S.set_option(31, 0)                    # the bottom of the V-cycle through global memory (the form before wl_set_option(31))
+    S.set_option(S.Opt.COARSE_PCG_RESIDENT, 0)   # the bottom of the V-cycle through global memory (the form before this key)
     for _ in range(5):
         S.sim_step(s, remeasure=False)
     torch.cuda.synchronize(); t0 = time.perf_counter()
     for _ in range(K):
         S.sim_step(s, remeasure=False)
     torch.cuda.synchronize(); dt0 = (time.perf_counter() - t0) / K
-    S.set_option(31, 1)
-    print(f"{dims} {np.dtype(T).name}: {dt * 1e3:.3f} ms/step = {np.prod(dims) / dt / 1e6:.1f} MLUPS, V-cycles {s.pois.n[-2:]}   (option 31 off: {dt0 * 1e3:.3f} ms)", flush=True)
+    S.set_option(S.Opt.COARSE_PCG_RESIDENT, 1)
+    print(f"{dims} {np.dtype(T).name}: {dt * 1e3:.3f} ms/step = {np.prod(dims) / dt / 1e6:.1f} MLUPS, V-cycles {s.pois.n[-2:]}   (COARSE_PCG_RESIDENT off: {dt0 * 1e3:.3f} ms)", flush=True)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-kernel-class time of one sim_step! on the BASELINE sphere, A/B over one wl_set_option key, in ONE process.
-usage: classes.py <size> <key> [reps] [dtype] [valA valB]   (default values 1 0)"""
+usage: classes.py <size> <key> [reps] [dtype] [valA valB]   (default values 1 0; e.g. classes.py 512 ROW_CONST_L; a key is a name or a number: BDIM_IN_CONVDIFF or 27)"""
 import ctypes as C
 import os
 import sys
@@ -14,7 +14,7 @@ from waterlily_amd import _lib  # noqa: E402
 from waterlily_amd import sim as S  # noqa: E402
 
 size = int(sys.argv[1]) if len(sys.argv) > 1 else 512
-key = int(sys.argv[2]) if len(sys.argv) > 2 else 9
+key = S.opt_key(sys.argv[2]) if len(sys.argv) > 2 else S.Opt.ROW_CONST_L
 reps = int(sys.argv[3]) if len(sys.argv) > 3 else 2
 T = np.float64 if (len(sys.argv) > 4 and sys.argv[4] == "f64") else np.float32
 VA, VB = (int(sys.argv[5]), int(sys.argv[6])) if len(sys.argv) > 6 else (1, 0)
@@ -40,7 +40,7 @@ for r in range(reps):
             res.setdefault((nm, val), []).append((ms.value, nl.value))
         _lib.check(L.wl_prof_select(-1, 0))
 _lib.check(L.wl_set_option(key, VA))
-print(f"{size}^3 {T.__name__}: per-class ms per step (launches), option[{key}] = {VA} | {VB};  uniform rows level 0: {S.uniform_rows(sim.pois, 0)}")
+print(f"{size}^3 {T.__name__}: per-class ms per step (launches), {S.opt_name(key)} = {VA} | {VB};  uniform rows level 0: {S.uniform_rows(sim.pois, 0)}")
 for nm in classes:
     if (nm, VA) not in res:
         continue

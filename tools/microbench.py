@@ -11,6 +11,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from waterlily_amd import _lib  # noqa: E402
 from waterlily_amd import sim as S  # noqa: E402
+from waterlily_amd.sim import Opt  # noqa: E402
 
 size = int(sys.argv[1]) if len(sys.argv) > 1 else 512
 reps = int(sys.argv[2]) if len(sys.argv) > 2 else 5
@@ -41,39 +42,39 @@ def ab(title, kclass, key, fn, algT, vals=(1, 0), restore=1):
     res = {v: [] for v in vals}
     for r in range(reps):
         for val in vals:
-            _lib.check(L.wl_set_option(key, val))
+            S.set_option(key, val)
             S.residual(ml)
             t, n = timed(kclass, fn)
             res[val].append(t)
-    _lib.check(L.wl_set_option(key, restore))
+    S.set_option(key, restore)
     for val in vals:
         t = float(np.median(res[val]))
-        print(f"{title:28s} option[{key}]={val}: {t:7.3f} ms/launch  {algT * 4 * ncell / max(t, 1e-9) / 1e6:7.0f} GB/s alg ({n} launches)")
+        print(f"{title:28s} {key.name}={val}: {t:7.3f} ms/launch  {algT * 4 * ncell / max(t, 1e-9) / 1e6:7.0f} GB/s alg ({n} launches)")
 
 
-ab("pcg mult+dot (6T)", "pcg_mult_dot", 0, lambda: S.pcg(ml), 6)
-ab("increment (9T)", "increment", 0, lambda: S.increment(ml), 9)
-ab("residual (8T)", "residual", 0, lambda: S.residual(ml), 8)
-ab("V-cycle smoother (9T)", "smooth", 1, lambda: S.Vcycle(ml), 9)
-print("-- option[4]: rows per thread of the 7-point kernel (1 | 2)")
-ab("pcg mult+dot (6T)", "pcg_mult_dot", 4, lambda: S.pcg(ml), 6, (1, 2), 0)
-ab("increment (9T)", "increment", 4, lambda: S.increment(ml), 9, (1, 2), 0)
-ab("residual (8T)", "residual", 4, lambda: S.residual(ml), 8, (1, 2), 0)
-ab("V-cycle smoother (9T)", "smooth", 4, lambda: S.Vcycle(ml), 9, (1, 2), 0)
+ab("pcg mult+dot (6T)", "pcg_mult_dot", Opt.STENCIL7_VEC, lambda: S.pcg(ml), 6)
+ab("increment (9T)", "increment", Opt.STENCIL7_VEC, lambda: S.increment(ml), 9)
+ab("residual (8T)", "residual", Opt.STENCIL7_VEC, lambda: S.residual(ml), 8)
+ab("V-cycle smoother (9T)", "smooth", Opt.SMOOTH_FUSED, lambda: S.Vcycle(ml), 9)
+print("-- STENCIL7_ROWS: rows per thread of the 7-point kernel (1 | 2)")
+ab("pcg mult+dot (6T)", "pcg_mult_dot", Opt.STENCIL7_ROWS, lambda: S.pcg(ml), 6, (1, 2), 0)
+ab("increment (9T)", "increment", Opt.STENCIL7_ROWS, lambda: S.increment(ml), 9, (1, 2), 0)
+ab("residual (8T)", "residual", Opt.STENCIL7_ROWS, lambda: S.residual(ml), 8, (1, 2), 0)
+ab("V-cycle smoother (9T)", "smooth", Opt.STENCIL7_ROWS, lambda: S.Vcycle(ml), 9, (1, 2), 0)
 for nm in ("pcg_update", "pcg_direction", "pcg_init"):
     t, n = timed(nm, lambda: S.pcg(ml))
     print(f"{nm:28s} {t:7.3f} ms/launch ({n} launches)")
 
-# BDIM! inside mom_step (option 3 = body-free row flags): needs a body
+# BDIM! inside mom_step (BDIM_ROWFLAGS = body-free row flags): needs a body
 import bench  # noqa: E402
 sim = bench.sphere((size,) * 3, T)
 for val in (1, 0, 1, 0):
-    _lib.check(L.wl_set_option(3, val))
+    S.set_option(Opt.BDIM_ROWFLAGS, val)
     t, n = timed("bdim", lambda: S.sim_step(sim, remeasure=False))
-    print(f"BDIM!#2 in mom_step          option[3]={val}: {t:7.3f} ms/launch ({n} launches)")
-_lib.check(L.wl_set_option(3, 1))
+    print(f"BDIM!#2 in mom_step          BDIM_ROWFLAGS={val}: {t:7.3f} ms/launch ({n} launches)")
+S.set_option(Opt.BDIM_ROWFLAGS, 1)
 for val in (1, 0, 1, 0):
-    _lib.check(L.wl_set_option(2, val))
+    S.set_option(Opt.CONVDIFF_TILED, val)
     t, n = timed("conv_diff", lambda: S.sim_step(sim, remeasure=False))
-    print(f"conv_diff!+BDIM!#1           option[2]={val}: {t:7.3f} ms/launch ({n} launches)")
-_lib.check(L.wl_set_option(2, 1))
+    print(f"conv_diff!+BDIM!#1           CONVDIFF_TILED={val}: {t:7.3f} ms/launch ({n} launches)")
+S.set_option(Opt.CONVDIFF_TILED, 1)

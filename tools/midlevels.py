@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Time of ONE pcg!(it=6) call on a level of n^3 cells (the multigrid levels below the finest one), as the finest level of
 its own small hierarchy: mean over `reps` calls, r restored before each call (the copy is timed separately and
-subtracted).  usage: midlevels.py [--f64] [key=v1,v2,...]   e.g.  midlevels.py 15=0,1   (key 24, the partial budget swept in round 3, is a constant now)"""
+subtracted).  usage: midlevels.py [--f64] [key=v1,v2,...]   e.g.  midlevels.py PCG_DOTS_IN_KERNEL=0,1
+(a key is a name or a number; key 24, the partial budget swept in round 3, is a constant now)"""
 import ctypes as C
 import os
 import sys
@@ -16,7 +17,7 @@ from waterlily_amd import sim as S  # noqa: E402
 
 T = np.float64 if "--f64" in sys.argv else np.float32
 sweep = [a for a in sys.argv[1:] if "=" in a]
-key, vals = (int(sweep[0].split("=")[0]), [int(v) for v in sweep[0].split("=")[1].split(",")]) if sweep else (15, [1])
+key, vals = (S.opt_key(sweep[0].split("=")[0]), [int(v) for v in sweep[0].split("=")[1].split(",")]) if sweep else (S.Opt.PCG_DOTS_IN_KERNEL, [1])
 L = _lib.lib()
 reps = 50
 
@@ -33,7 +34,7 @@ def timed(fn):
     return a.elapsed_time(b) / reps * 1e3     # us
 
 
-print(f"pcg!(it=6) on an n^3 level, {np.dtype(T).name}: us per call (18 dependent kernels as launched today); option[{key}] sweep")
+print(f"pcg!(it=6) on an n^3 level, {np.dtype(T).name}: us per call (18 dependent kernels as launched today); {S.opt_name(key)} sweep")
 for n in (256, 128, 64, 32):
     U = (1.0, 0.0, 0.0)
     a = S.Flow((n, n, n), U, T=T)

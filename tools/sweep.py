@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-launch time of the finest-level kernel classes on the BASELINE sphere for several values of one
-wl_set_option key, in ONE process.  usage: sweep.py <size> <key> <v1> <v2> ... [--f64]
+wl_set_option key, in ONE process.  usage: sweep.py <size> <key> <v1> <v2> ... [--f64]   (e.g. sweep.py 512 STREAM_GRID_K 8 16 32; a key is a name or a number: BDIM_IN_CONVDIFF or 27)
 env: WL_CLASSES=a,b,..  WL_MINFRAC=0.5 (launches of at least this share of the cells; 0 = every launch of the class)
 WL_TOTAL=1 (ms per step summed over the selected launches instead of the per-launch mean)"""
 import ctypes as C
@@ -17,18 +17,18 @@ from waterlily_amd import sim as S  # noqa: E402
 
 argv = [a for a in sys.argv[1:] if a != "--f64"]
 T = np.float64 if "--f64" in sys.argv else np.float32
-size, key = int(argv[0]), int(argv[1])
+size, key = int(argv[0]), S.opt_key(argv[1])
 vals = [int(v) for v in argv[2:]]
 L = _lib.lib()
-for kv in os.environ.get("WL_PRESET", "").split(","):   # options that must be set BEFORE the handles are created, "5=1,..."
+for kv in os.environ.get("WL_PRESET", "").split(","):   # options that must be set BEFORE the handles are created, "PCG_VEC=1,..."
     if "=" in kv:
-        _lib.check(L.wl_set_option(int(kv.split("=")[0]), int(kv.split("=")[1])))
+        S.set_option(kv.split("=")[0], int(kv.split("=")[1]))
 sim = bench.sphere((size,) * 3, T)
 names = {L.wl_kernel_name(k).decode(): k for k in range(24)}
 for _ in range(int(os.environ.get("WL_PRESTEPS", "30"))):
     S.sim_step(sim, remeasure=False)
 classes = os.environ.get("WL_CLASSES", "pcg_mult_dot,pcg_update,pcg_direction,smooth,residual").split(",")
-print(f"{size}^3 {T.__name__} option[{key}] sweep; ms per finest-level launch")
+print(f"{size}^3 {T.__name__} {S.opt_name(key)} sweep; ms per finest-level launch")
 print("value  " + "  ".join(f"{c:>13s}" for c in classes))
 for rep in range(2):
     for v in vals:

@@ -16,25 +16,22 @@ from waterlily_amd import sim as S  # noqa: E402
 n = int(sys.argv[1])
 T = np.float64 if "--f64" in sys.argv else np.float32
 mk = bench.donut if "--donut" in sys.argv else bench.sphere
-KEYS = (3, 8, 9, 13, 14, 18, 19, 22, 23, 30)
+Opt = S.Opt
+KEYS = (Opt.BDIM_ROWFLAGS, Opt.PCG_DEFER_X, Opt.ROW_CONST_L, Opt.PCG_RECOMPUTE_PRECOND, Opt.SCALE_CHAIN, Opt.CONVDIFF_SHARED_FLUX,
+        Opt.PCG_RECOMPUTE_AEPS, Opt.DIV_IN_RESIDUAL, Opt.XGHOST_IN_KERNEL, Opt.SWEEP_ALTERNATE)   # the traffic-saving forms
 
 
 def run(off=()):
-    for k in off:
-        S.set_option(k, 0)
-    try:
+    with S.options({k: 0 for k in off}):
         sim = mk((n, n, n), T)
         for _ in range(3):
             S.sim_step(sim, remeasure=False)
-    finally:
-        for k in off:
-            S.set_option(k, 1)
     return sim.pois.n[:], list(sim.flow.dt), S.copy_of(sim.flow.u)
 
 
 base = run()
 print("defaults again:", end=" ")
-for name, off in [("same", ())] + [(str(k), (k,)) for k in KEYS]:
+for name, off in [("same", ())] + [(k.name, (k,)) for k in KEYS]:
     r = run(off)
     du = float((r[2] - base[2]).abs().max())
-    print(f"off={name:4s} n_equal={r[0] == base[0]} dt_equal={r[1] == base[1]} max|du|={du:.3e}", flush=True)
+    print(f"off={name:22s} n_equal={r[0] == base[0]} dt_equal={r[1] == base[1]} max|du|={du:.3e}", flush=True)

@@ -4,7 +4,9 @@ There is NO fallback: if the HIP library is missing or a call fails, an exceptio
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
+import enum
 import os
 import re
 import subprocess
@@ -47,6 +49,53 @@ class BodyDesc(C.Structure):
 WL_BODY_SPHERE, WL_BODY_TORUS, WL_BODY_PLATE, WL_BODY_CYLINDER = 0, 1, 2, 3
 WL_BODY_OP_UNION, WL_BODY_OP_MINUS, WL_BODY_OP_INTERSECT = 0, 1, 2
 WL_BODY_MAXLEAF = 6
+
+
+class Opt(enum.IntEnum):
+    """wl_set_option keys: the WL_OPT_* enumerators of include/wlhip.h (tests/test_options.py holds the two together)."""
+    STENCIL7_VEC = 0
+    SMOOTH_FUSED = 1
+    CONVDIFF_TILED = 2
+    BDIM_ROWFLAGS = 3
+    STENCIL7_ROWS = 4
+    PCG_VEC = 5
+    COARSE_TAIL = 6
+    BC_FUSED = 7
+    PCG_DEFER_X = 8
+    ROW_CONST_L = 9
+    PCG_START_FUSED = 10
+    PCG_RECOMPUTE_PRECOND = 13
+    SCALE_CHAIN = 14
+    PCG_DOTS_IN_KERNEL = 15
+    STENCIL7_GRID_K = 16
+    STREAM_GRID_K = 17
+    CONVDIFF_SHARED_FLUX = 18
+    PCG_RECOMPUTE_AEPS = 19
+    DIV_IN_RESIDUAL = 22
+    XGHOST_IN_KERNEL = 23
+    MBOX_TIMEOUT_S = 26
+    BDIM_IN_CONVDIFF = 27
+    SWEEP_ALTERNATE = 30
+    COARSE_PCG_RESIDENT = 31
+
+
+def opt_key(key) -> int:
+    """A wl_set_option key given as an Opt, a number, or a name ("PCG_VEC", "WL_OPT_PCG_VEC", "5"): the number.
+    Numbers pass unchecked (the library refuses the ones it does not know)."""
+    if isinstance(key, str) and not key.strip().lstrip("+-").isdigit():
+        name = key.strip().upper()
+        name = name[len("WL_OPT_"):] if name.startswith("WL_OPT_") else name
+        if name not in Opt.__members__:
+            raise WlError(f"no such option: {key!r} (one of {', '.join(Opt.__members__)})")
+        return int(Opt[name])
+    return int(key)
+
+
+def opt_name(key) -> str:
+    """How a tool prints a key: NAME (number)"""
+    k = opt_key(key)
+    return f"{Opt(k).name} ({k})" if k in Opt._value2member_map_ else str(k)
+
 
 SENDRECV_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int)
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_int, C.c_int)
@@ -187,6 +236,31 @@ def check(rc: int) -> None:
         if rc == WL_E_LEVELS:
             raise AssertionError("MultiLevelPoisson requires size=a2ⁿ, where n>2")
         raise WlError(f"libwlhip call failed ({rc}): {msg}")
+
+
+def set_option(key, value: int):
+    """Tuning / A-B switches of the library (include/wlhip.h, wl_set_option); key: an Opt, its number or its name."""
+    check(lib().wl_set_option(opt_key(key), int(value)))
+
+
+def get_option(key) -> int:
+    v = C.c_int()
+    check(lib().wl_get_option(opt_key(key), C.byref(v)))
+    return v.value
+
+
+@contextlib.contextmanager
+def options(values):
+    """`with options({Opt.PCG_DEFER_X: 0, ...}):` sets the given keys and puts the values they HAD back on the way out,
+    exception or not."""
+    keep = {k: get_option(k) for k in values}
+    try:
+        for k, v in values.items():
+            set_option(k, v)
+        yield
+    finally:
+        for k, v in keep.items():
+            set_option(k, v)
 
 
 def d3(v):

@@ -265,7 +265,7 @@ struct wl_flow {
     unsigned char *rowbuf = nullptr;
     unsigned char *segbuf = nullptr;    // the same per 64-cell segment of a row (3-D; wl_flow_update's scan only)
     bool seg_valid = false;
-    const unsigned char *segfree() const { return (seg_valid && ctx().opt[3]) ? segbuf : nullptr; }
+    const unsigned char *segfree() const { return (seg_valid && opt(WL_OPT_BDIM_ROWFLAGS)) ? segbuf : nullptr; }
     int *busy = nullptr;                // compact list of the busy interior rows (j + n1*k), device
     int nbusy = 0;
     int nbusy_lo = 0, nbusy_hi = 0;      // how many of them lie in the first / last owned interior plane (the list is sorted by plane)
@@ -286,7 +286,7 @@ template <class T> static LevelT<T> lvl(const wl_mg *m, int l) {
     LevelT<T> o;
     o.g = mkG(&d.g);
     o.L = (T *)d.L; o.D = (T *)d.D; o.iD = (T *)d.iD; o.x = (T *)d.x; o.eps = (T *)d.eps; o.r = (T *)d.r; o.z = (T *)d.z;
-    o.rowc = (ctx().opt[9] && l < (int)m->rowc.size()) ? (const T *)m->rowc[l] : nullptr;
+    o.rowc = (opt(WL_OPT_ROW_CONST_L) && l < (int)m->rowc.size()) ? (const T *)m->rowc[l] : nullptr;
     return o;
 }
 
@@ -316,7 +316,7 @@ template <class T, int D> static int mg_update(wl_mg *m, const unsigned char *di
 // pcg! that the caller runs next on level l (eps = r*iD, rho partials), else -1
 template <class T, int D> static int mg_vcycle(wl_mg *m, int l, int *pcg_np = nullptr) {
     LevelT<T> fine = lvl<T>(m, l), coarse = lvl<T>(m, l + 1);
-    const bool fused = (m->permask == 0) && ctx().opt[1];   // periodic ghosts of eps are copies, not zeros: keep the two-pass form
+    const bool fused = (m->permask == 0) && opt(WL_OPT_SMOOTH_FUSED);   // periodic ghosts of eps are copies, not zeros: keep the two-pass form
     if (fused) WL_TRY((op_smooth_fused<T, D>(fine, fine.eps)));     // r' lives in the eps buffer until the way up
     else WL_TRY((op_jacobi<T, D>(fine, 1, m->permask)));
     // fill!(coarse.x, 0) (MultiLevelPoisson.jl:75) rides in the restriction kernel where the level's ghost cells cannot
@@ -333,8 +333,8 @@ template <class T, int D> static int mg_vcycle(wl_mg *m, int l, int *pcg_np = nu
         WL_HIP(hipMemsetAsync(coarse.x, 0, (size_t)span(coarse.g) * sizeof(T), ctx().stream));
     }
     // levels <= 4096 cells: the rest of the recursion + smooth!(coarse) as ONE single-workgroup launch (wl_coarse.h)
-    const long tail_cells = ctx().opt[6] == 1 ? CV_MAXCELLS : ctx().opt[6];   // option 6: 0 off, 1 default, else threshold
-    bool tail = ctx().opt[6] && fused && !coarse.g.dist && coarse.g.interior_cells() <= tail_cells && (m->nlev - (l + 1)) <= CV_MAXLEV;
+    const long tail_cells = coarse_tail_cells();
+    bool tail = tail_cells && fused && !coarse.g.dist && coarse.g.interior_cells() <= tail_cells && (m->nlev - (l + 1)) <= CV_MAXLEV;
     if (tail) {
         CoarseArgs<T> ca;
         ca.nlev = m->nlev - (l + 1);
@@ -344,7 +344,7 @@ template <class T, int D> static int mg_vcycle(wl_mg *m, int l, int *pcg_np = nu
         }
         if (tail) {
             Prof p(WL_K_SMOOTH, coarse.g.cells());
-            if (ctx().opt[31]) hipLaunchKernelGGL((k_coarse_vcycle<T, D, true>), dim3(1), dim3(CV_THREADS), 0, ctx().stream, ca);
+            if (opt(WL_OPT_COARSE_PCG_RESIDENT)) hipLaunchKernelGGL((k_coarse_vcycle<T, D, true>), dim3(1), dim3(CV_THREADS), 0, ctx().stream, ca);
             else hipLaunchKernelGGL((k_coarse_vcycle<T, D, false>), dim3(1), dim3(CV_THREADS), 0, ctx().stream, ca);
             WL_HIP(hipGetLastError());
         }
@@ -420,9 +420,9 @@ template <class T, int D> static int flow_project(wl_flow *a, wl_mg *b, double d
     const double dts = sc.s;
     const bool dbl = sc.dbl;
     const Range R = r_inside(g);
-    // 3-D vector kernels: z = div(u) is formed inside residual! (wl_set_option(22)); p.z stays unwritten
+    // 3-D vector kernels: z = div(u) is formed inside residual! (WL_OPT_DIV_IN_RESIDUAL); p.z stays unwritten
     // (rowvec_fits: a plane's workgroups fit the partial buffer -- the launch below cannot be rejected for its size)
-    const bool fused_div = D == 3 && ctx().opt[22] && ctx().opt[5] && stencil7_ok<T>(g) && stencil7_ok<T>(p.g) && rowvec_fits<T>(p.g) && b->permask == 0 &&
+    const bool fused_div = D == 3 && opt(WL_OPT_DIV_IN_RESIDUAL) && pcg_vec_ok<T>(g) && stencil7_ok<T>(p.g) && rowvec_fits<T>(p.g) && b->permask == 0 &&
                            g.s[1] == p.g.s[1] && g.s[2] == p.g.s[2] && g.n[0] == p.g.n[0] && g.n[2] == p.g.n[2] && g.dist == p.g.dist;
     bool begun = false;
     if (fused_div && g.dist) {
@@ -455,10 +455,10 @@ static int flow_mom_step(wl_flow *a, wl_mg *b, double dt, const double *U, const
     const G g = mkG(&d.g);
     T *u = (T *)d.u, *u0 = (T *)d.u0, *f = (T *)d.f, *V = (T *)d.V, *mu0 = (T *)d.mu0, *mu1 = (T *)d.mu1;
     // (z-slab runs: u carries a 2-plane halo for QUICK, f a 1-plane halo for mu_ddn; exchanges are no-ops otherwise)
-    // (the x-ghost cells of the interior rows are written by the kernel that produces the row: XBc, wl_set_option(23))
-    const XBc<T> xbc{(D == 3 && d.perdir_mask == 0 && ctx().opt[7] && ctx().opt[23]) ? 1 : 0, d.exitBC ? 1 : 0, (T)U[0]};
+    // (the x-ghost cells of the interior rows are written by the kernel that produces the row: XBc, WL_OPT_XGHOST_IN_KERNEL)
+    const XBc<T> xbc{(D == 3 && d.perdir_mask == 0 && opt(WL_OPT_BC_FUSED) && opt(WL_OPT_XGHOST_IN_KERNEL)) ? 1 : 0, d.exitBC ? 1 : 0, (T)U[0]};
     bool xd = false;
-    // `turns`: BDIM! is finished inside conv_diff! on the body-free rows (wl_set_option(27), CdFin in wl_convdiff.h).  The kernel
+    // `turns`: BDIM! is finished inside conv_diff! on the body-free rows (WL_OPT_BDIM_IN_CONVDIFF, CdFin in wl_convdiff.h).  The kernel
     // that forms f cannot overwrite the velocity its neighbours still read, so the two velocity arrays take turns: the predictor
     // reads `u` (which thereby IS u0: no copy) and writes u' into the flow's u0 array; the corrector reads u' there and u0 in
     // `u`, cell by cell, and writes the new velocity over it.  On return `u` holds the new velocity as always and the u0 ARRAY
@@ -467,7 +467,7 @@ static int flow_mom_step(wl_flow *a, wl_mg *b, double dt, const double *U, const
     // and BDIM! #2 is a pass of its own, in place.
     bool turns = false;
     if constexpr (D == 3)
-        turns = ctx().opt[27] && ctx().opt[3] && a->rowfree && a->busy && d.perdir_mask == 0 && !d.exitBC && conv_diff_tiled<D>(g, 0);
+        turns = opt(WL_OPT_BDIM_IN_CONVDIFF) && opt(WL_OPT_BDIM_ROWFLAGS) && a->rowfree && a->busy && d.perdir_mask == 0 && !d.exitBC && conv_diff_tiled<D>(g, 0);
     T *const up = turns ? u0 : u;   // where the predictor's velocity u' lives
     const CdFin<T> fin1{up, a->rowfree, xbc.on, (T)U[0]}, fin2{u, a->rowfree, xbc.on, (T)U[0]};
     (void)fin1; (void)fin2;
@@ -491,7 +491,7 @@ static int flow_mom_step(wl_flow *a, wl_mg *b, double dt, const double *U, const
     if (d.exitBC) WL_TRY((op_exit_bc<T, D>(g, up, u0, U, dt, a->sc.partials, a->sc.st)));
     // (the predictor's closing `x ./= dt` and the corrector's opening `x .*= 0.5dt` are ONE pass over x: nothing in between reads p)
     const ScaleOp corr_head = project_scale<T>(dt, 0.5);
-    const bool chain = ctx().opt[14] != 0;
+    const bool chain = opt(WL_OPT_SCALE_CHAIN) != 0;
     WL_TRY((flow_project<T, D>(a, b, dt, 1.0, &n2[0], true, false, chain ? &corr_head : nullptr, &xbc, &xd, up)));   // + 1-plane exchange of u' (overlapped)
     WL_TRY((op_bc_vec<T, D>(g, up, U, d.exitBC, d.perdir_mask, xd)));
     // corrector (:164-167); the 2-plane exchange of u' is issued inside op_conv_diff (overlapped with its inner planes);
@@ -1507,12 +1507,12 @@ int wl_snapshot_unpack(wl_dtype t, const wl_grid *g, void *a, int ncomp, int ntu
 
 int wl_set_option(int key, int value) {
     if (key < 0 || key >= 32 || !((WL_OPT_LIVE >> key) & 1u)) return fail(WL_E_ARG, "wl_set_option: no such option", __FILE__, __LINE__);
-    ctx().opt[key] = value;
+    ctx().opt.v[key] = value;
     return 0;
 }
 int wl_get_option(int key, int *value) {
     if (!value || key < 0 || key >= 32 || !((WL_OPT_LIVE >> key) & 1u)) return fail(WL_E_ARG, "wl_get_option: no such option", __FILE__, __LINE__);
-    *value = ctx().opt[key];
+    *value = opt(key);
     return 0;
 }
 

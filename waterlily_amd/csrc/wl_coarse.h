@@ -16,6 +16,8 @@
 namespace wl {
 
 constexpr int CV_THREADS = 1024, CV_MAXLEV = 8, CV_MAXCELLS = 4096;
+// WL_OPT_COARSE_TAIL: the largest level (interior cells) the tail starts on; 0 = off, 1 (default) = CV_MAXCELLS, else the value
+inline long coarse_tail_cells() { return opt(WL_OPT_COARSE_TAIL) == 1 ? CV_MAXCELLS : opt(WL_OPT_COARSE_TAIL); }
 
 template <class T> struct CoarseArgs {
     int nlev;
@@ -169,7 +171,7 @@ template <class T, int D> __device__ void cv_pcg(const LevelT<T> &p, double *sm)
     }
 }
 
-// pcg!(p; it=6) with the level held ON CHIP (wl_set_option(31), default on): a thread keeps r, x, z, eps, iD and the face
+// pcg!(p; it=6) with the level held ON CHIP (WL_OPT_COARSE_PCG_RESIDENT, default on): a thread keeps r, x, z, eps, iD and the face
 // coefficients of its <= 4 cells in registers for the whole call; only eps -- the one operand neighbours read -- lives in
 // LDS (ghost cells 0: non-periodic levels).  The phases of an iteration then wait for LDS (~0.1 us) instead of for stores
 // to reach L2 and come back (~1 us each, three per iteration).  Same per-cell expressions, same order of every sum as

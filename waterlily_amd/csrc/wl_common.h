@@ -68,10 +68,28 @@ struct Mailbox {
     int *err_host = nullptr, *err_dev = nullptr;   // set by a kernel that gave up waiting for a peer
 };
 
+// wl_set_option (names and meaning: include/wlhip.h): THE table of keys and defaults.  A key is live when it has a row;
+// the initial values of Ctx::opt and the mask wl_set_option checks are derived from it.
+struct OptRow { int key, def; };
+constexpr OptRow WL_OPT_ROWS[] = {
+    {WL_OPT_STENCIL7_VEC, 1},         {WL_OPT_SMOOTH_FUSED, 1},       {WL_OPT_CONVDIFF_TILED, 1},  {WL_OPT_BDIM_ROWFLAGS, 1},
+    {WL_OPT_STENCIL7_ROWS, 0},        {WL_OPT_PCG_VEC, 2},            {WL_OPT_COARSE_TAIL, 1},     {WL_OPT_BC_FUSED, 1},
+    {WL_OPT_PCG_DEFER_X, 1},          {WL_OPT_ROW_CONST_L, 1},        {WL_OPT_PCG_START_FUSED, 1}, {WL_OPT_PCG_RECOMPUTE_PRECOND, 1},
+    {WL_OPT_SCALE_CHAIN, 1},          {WL_OPT_PCG_DOTS_IN_KERNEL, 1}, {WL_OPT_STENCIL7_GRID_K, 4}, {WL_OPT_STREAM_GRID_K, 16},
+    {WL_OPT_CONVDIFF_SHARED_FLUX, 1}, {WL_OPT_PCG_RECOMPUTE_AEPS, 1}, {WL_OPT_DIV_IN_RESIDUAL, 1}, {WL_OPT_XGHOST_IN_KERNEL, 1},
+    {WL_OPT_MBOX_TIMEOUT_S, 600},     {WL_OPT_BDIM_IN_CONVDIFF, 1},   {WL_OPT_SWEEP_ALTERNATE, 1}, {WL_OPT_COARSE_PCG_RESIDENT, 1},
+};
+struct Opts { int v[32] = {}; };
+constexpr Opts opt_defaults() { Opts o; for (const OptRow &r : WL_OPT_ROWS) o.v[r.key] = r.def; return o; }
+constexpr unsigned opt_live() { unsigned m = 0; for (const OptRow &r : WL_OPT_ROWS) m |= 1u << r.key; return m; }
+constexpr int opt_bits(unsigned m) { int n = 0; for (; m; m &= m - 1) ++n; return n; }
+constexpr unsigned WL_OPT_LIVE = opt_live();
+static_assert(WL_OPT_LIVE == 0xCCCFE7FFu, "the set of live wl_set_option keys changed: update this mask, include/wlhip.h and Opt in _lib.py");
+static_assert(opt_bits(WL_OPT_LIVE) == (int)(sizeof(WL_OPT_ROWS) / sizeof(WL_OPT_ROWS[0])), "a wl_set_option key has two rows");
+
 struct Ctx {
     Mailbox *mbox = nullptr;
-    // wl_set_option (include/wlhip.h); keys 11, 12, 20, 21, 24, 25, 28, 29 are retired (WL_OPT_LIVE)
-    int opt[32] = {1, 1, 1, 1, 0, 2, 1, 1, 1, 1, 1, 0, 0, 1, 1, 1, 4, 16, 1, 1, 0, 0, 1, 1, 0, 0, 600, 1, 0, 0, 1, 1};
+    Opts opt = opt_defaults();
     double wall_khz = 0.0;             // rate of the device's wall clock (mailbox time-outs), read when the mailbox is made
     Comm *comm = nullptr;
     hipStream_t stream = nullptr;
@@ -92,11 +110,10 @@ struct Ctx {
     int64_t n_alloc = 0, alloc_bytes = 0;   // device + pinned-host allocations the library has made (wl_prof_allocs)
 };
 Ctx &ctx();
+inline int opt(int key) { return ctx().opt.v[key]; }   // current value of WL_OPT_<key>
 // every allocation of the library goes through these two (counted: a steady time step must not allocate, test/alloctest.jl)
 inline hipError_t wl_dev_alloc(void **p, size_t n) { ctx().n_alloc += 1; ctx().alloc_bytes += (int64_t)n; return hipMalloc(p, n); }
 inline hipError_t wl_host_alloc(void **p, size_t n, unsigned flags) { ctx().n_alloc += 1; ctx().alloc_bytes += (int64_t)n; return hipHostMalloc(p, n, flags); }
-// live wl_set_option keys: 0-10, 13-19, 22, 23, 26, 27, 30, 31
-constexpr unsigned WL_OPT_LIVE = 0xCCCFE7FFu;
 int fail(int code, const char *what, const char *file, int line);
 
 #define WL_HIP(expr)                                                        \
@@ -377,7 +394,7 @@ template <class FIN> __global__ void k_apply(const double *red, FIN fin) { fin(r
 // local reduction (exactly k_reduce_only) + the exchange through the mailbox: red[q] = op over the ranks, in rank order.
 // Slot (seq & 1, rank) is written by its owner only; a rank can be at most one all-reduce ahead of the slowest one (it
 // needs that rank's value of the current round to finish it), so two parities suffice.  A wait is bounded in WALL-CLOCK
-// time (wl_set_option(26) seconds on the device's constant-rate clock, default 600; 0 = wait for ever, like a collective
+// time (WL_OPT_MBOX_TIMEOUT_S seconds on the device's constant-rate clock, default 600; 0 = wait for ever, like a collective
 // would): a lane that gives up raises the error flag (the host turns it into an error at its next synchronisation) and the
 // values become NaN -- the grid always drains.  Ranks may legitimately be apart by the length of rank-asymmetric host work
 // (a first-call compile, geometry, file output): the default leaves minutes for that.
@@ -436,7 +453,7 @@ template <int NV> inline int reduce_allreduce(const double *partials, int np, in
         cm->cnt[0] += 1;
         mb->seq += 1;
         hipLaunchKernelGGL((k_reduce_mbox<NV>), dim3(1), dim3(WL_FIN_T), 0, ctx().stream, partials, np, op, init, red, mb->dev, cm->rank,
-                           cm->size, mb->seq, mb->err_dev, (long long)((double)(ctx().opt[26] > 0 ? ctx().opt[26] : 0) * ctx().wall_khz * 1e3));
+                           cm->size, mb->seq, mb->err_dev, (long long)((double)(opt(WL_OPT_MBOX_TIMEOUT_S) > 0 ? opt(WL_OPT_MBOX_TIMEOUT_S) : 0) * ctx().wall_khz * 1e3));
         return (int)hipGetLastError();
     }
     hipLaunchKernelGGL((k_reduce_only<NV>), dim3(1), dim3(WL_FIN_T), 0, ctx().stream, partials, np, op, init, red);
@@ -657,14 +674,14 @@ inline int halo_end() {
     return 0;
 }
 
-// Consecutive marching kernels sweep in OPPOSITE directions (wl_set_option(30)): each XCD keeps its range of tiles -- its slab
+// Consecutive marching kernels sweep in OPPOSITE directions (WL_OPT_SWEEP_ALTERNATE): each XCD keeps its range of tiles -- its slab
 // of the z axis, the same for every kernel -- but starts where the kernel before it stopped, on the lines that kernel has
 // just read or written and that still sit in the XCD's L2 and in the 256 MB Infinity Cache (a 512^3 Float32 array is
 // 537 MB: without the reversal every kernel begins on the lines that were evicted first).  The tile a workgroup takes
 // changes, the slot its reduction partial goes to stays that tile's: sums and fields are bit-identical either way.
 inline int sweep_rev() {
     Ctx &c = ctx();
-    if (!c.opt[30]) return 0;
+    if (!opt(WL_OPT_SWEEP_ALTERNATE)) return 0;
     c.sweep ^= 1;
     return c.sweep;
 }

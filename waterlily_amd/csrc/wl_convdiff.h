@@ -582,7 +582,7 @@ int launch_convdiff3(const G &g, T *r, const T *u, double nu_, const T *u0, T *u
     const bool use8 = sizeof(T) == 4;
     int thi_s = thi;
     if (use8 && ((thi_s - tlo + 1) & 1) && thi_s > tlo) --thi_s;   // 8-row tiles: an odd tile row goes to the shell
-    const bool shared = ctx().opt[18] != 0 && thi_s >= tlo && khi >= klo;
+    const bool shared = opt(WL_OPT_CONVDIFF_SHARED_FLUX) != 0 && thi_s >= tlo && khi >= klo;
     if (!shared) {
         const CdBox all{g.zlo, g.zhi, 0, nty_all};
         return launch_convdiff3_old<T, FUSE, COPY, FIN>(g, &all, 1, r, u, nu_, u0, u0out, V, dt_, a3, has_acc, fn);

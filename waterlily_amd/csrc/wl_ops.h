@@ -56,7 +56,7 @@ template <class T> __device__ __forceinline__ void xbc_apply(const XBc<T> &b, T 
 }
 template <class T, int D>
 int op_bc_vec(const G &g, T *a, const double *A, int saveexit, int permask, bool skip_x = false) {
-    if (ctx().opt[7]) return op_bc_vec_fused<T, D>(g, a, A, saveexit, permask, skip_x);   // one launch (closed form), see below
+    if (opt(WL_OPT_BC_FUSED)) return op_bc_vec_fused<T, D>(g, a, A, saveexit, permask, skip_x);   // one launch (closed form), see below
     if (skip_x) return fail(WL_E_STATE, "BC!: x planes folded into the producer need the one-launch form", __FILE__, __LINE__);
     for (int c = 0; c < D; ++c)
         for (int j = 0; j < D; ++j) {
@@ -431,7 +431,7 @@ int launch_convdiff_xghost(const G &g, T *r, const T *u, double nu_, const T *u0
 // stream, and the LDS kernel runs on the planes that read no halo plane (zlo+2 .. zhi-2) while it is in flight.
 // does op_conv_diff take the LDS-tiled kernels for this grid?
 template <int D> inline bool conv_diff_tiled(const G &g, int permask) {
-    return D == 3 && ctx().opt[2] && (permask == 0 || (permask == 4 && g.zring)) && g.n[0] >= 5 && g.n[1] >= 5 && g.n[2] >= 5;
+    return D == 3 && opt(WL_OPT_CONVDIFF_TILED) && (permask == 0 || (permask == 4 && g.zring)) && g.n[0] >= 5 && g.n[1] >= 5 && g.n[2] >= 5;
 }
 // FIN (1 predictor / 2 corrector, with `fin`): the tiled kernels also finish BDIM! on the body-free rows (CdFin, wl_convdiff.h);
 // only where conv_diff_tiled() holds.  The corrector's `fin->unew` is the array `u0` points to (every cell is read by the thread
@@ -585,7 +585,7 @@ int op_bdim2(const G &g, T *u, const T *f, const T *V, const T *mu0, const T *mu
              const int *busy = nullptr, int nbusy = 0, bool exchange_f = false, const XBc<T> *xbc = nullptr, bool *xdone = nullptr,
              const unsigned char *seg = nullptr) {
     const G gg = g;
-    if (!ctx().opt[3]) rowfree = nullptr;
+    if (!opt(WL_OPT_BDIM_ROWFLAGS)) rowfree = nullptr;
     if (xdone) *xdone = false;
     XBc<T> xb{0, 0, (T)0};
     if (xbc && xbc->on && rowfree && busy) xb = *xbc;   // both kernels below take part, or neither
@@ -812,7 +812,7 @@ template <class T, int D>
 int op_div(const G &g, T *z, const T *u, int klo = 0, int khi = -1) {   // [klo,khi]: optional local plane sub-range
     const G gg = g;
     if constexpr (D == 3) {
-        if (stencil7_ok<T>(g) && ctx().opt[5]) {   // 16-B vector form (same sums in the same order)
+        if (pcg_vec_ok<T>(g)) {   // 16-B vector form (same sums in the same order)
             using VA = VecA<T>;
             const int rc = launch_rowvec<T, 0, false>(WL_K_DIV, g,
                 [=] __device__(long o, int j, int k, const Pre &) { return face_load<T>(gg, u, o, j, k); },
@@ -988,7 +988,7 @@ _Pragma("unroll")
         if (exchange_u) WL_TRY((halo_exchange<T>(g, const_cast<T *>(u), D, 2)));
         int rcv = -1;
         if constexpr (D == 3) {
-            if (stencil7_ok<T>(g) && ctx().opt[5]) {   // 16-B vector form: same sums in the same order, max over the same cells
+            if (pcg_vec_ok<T>(g)) {   // 16-B vector form: same sums in the same order, max over the same cells
                 using VA = VecA<T>;
                 auto ld = [=] __device__(long o, int j, int k, const Pre &) { return face_load<T>(gg, u, o, j, k); };
                 auto st2 = [=] __device__(long o, int i, int, int, const FaceDat<T> &d, const auto &, double *acc, const Pre &) {
@@ -1268,7 +1268,7 @@ int op_prolong_increment_fused(const LevelT<T> &p, const T *rin, const G &gc, co
         if (stencil7_ok<T>(p.g)) {
             using VA = VecA<T>;
             const SrcProlong<T> src{cx, C, p.g.n[0], p.g.n[1], p.g.nzg, p.g.kz0};
-            if (pcg_np && partials && ctx().opt[10] && ctx().opt[13] && ctx().opt[5]) {
+            if (pcg_np && partials && opt(WL_OPT_PCG_START_FUSED) && opt(WL_OPT_PCG_RECOMPUTE_PRECOND) && opt(WL_OPT_PCG_VEC)) {
                 T *e0 = p.eps;
                 const int tpp = (((p.g.n[0] - 2 + 64 * VA::V - 1) / (64 * VA::V)) * ((p.g.n[1] - 2 + 3) / 4) + 7) / 8 * 8;
                 Gate gcap;
@@ -1330,7 +1330,7 @@ _Pragma("unroll")
 // device flag: once `active` drops, the remaining (already enqueued) kernels are no-ops, so no host sync.
 // Fusions: [mult + z.eps], [x,r update + z=r*iD + r.z], [direction]; identical per-cell arithmetic.
 // want_r2: the caller (solver!) needs L2(p) = r.r right after this call; it is accumulated by the last update kernel.
-// Deferred x (wl_set_option(8), default on): in iterations 1..it-1 the update x += alpha*eps (:133) moves from the
+// Deferred x (WL_OPT_PCG_DEFER_X, default on): in iterations 1..it-1 the update x += alpha*eps (:133) moves from the
 // update kernel into the direction kernel that follows it (which streams eps anyway): one array pass less per
 // iteration (10T instead of 11T for update+direction).  Same per-cell expression, alpha unchanged in between; the :138
 // exit leaves st->xpend so that the direction kernel still applies the owed x update and nothing else.
@@ -1468,6 +1468,19 @@ template <class T> struct PcgDots {
     void launched_direction() { if (form != PcgForm::FINALIZE) cur ^= 1; }
 };
 
+// WL_OPT_PCG_RECOMPUTE_AEPS on a level of `cells` interior cells: 1 (default) = levels of 2^22 .. 2^26 cells, 3 = every level
+// below 2^26, 2 = every level, 0 = never
+inline bool pcg_recompute_aeps(long cells) {
+    const int v = opt(WL_OPT_PCG_RECOMPUTE_AEPS);
+    return v == 2 || (v == 3 && cells < (1L << 26)) || (v == 1 && cells < (1L << 26) && cells >= (1L << 22));
+}
+// WL_OPT_PCG_DOTS_IN_KERNEL: 1 (default) = on levels of at most 2^25 cells, 2 = on every level, 0 = never; a z-slab run
+// (distr: the sums cross the ranks between the kernels either way) takes any non-zero value
+inline bool pcg_dots_in_kernel(long cells, bool distr) {
+    const int v = opt(WL_OPT_PCG_DOTS_IN_KERNEL);
+    return distr ? v != 0 : (v == 2 || (v == 1 && cells <= (1L << 25)));
+}
+
 template <class T, int D>
 int op_pcg(const LevelT<T> &p, int it, int permask, double *partials, State *st, bool want_r2 = false,
            int pre_np = -1,     // pre_np >= 0: eps = r*iD and the partials of rho are already there (op_prolong_increment_fused)
@@ -1477,33 +1490,29 @@ int op_pcg(const LevelT<T> &p, int it, int permask, double *partials, State *st,
     using VA = VecA<T>;
     const int n0 = p.g.n[0];
     // ---- which kernels
-    // streaming pcg kernels in 16-B vector form where the layout allows (wl_set_option(5,0) = scalar range kernels)
+    // streaming pcg kernels in 16-B vector form where the layout allows (WL_OPT_PCG_VEC = 0: scalar range kernels)
     bool vec = false;
-    if constexpr (D == 3) vec = ctx().opt[5] != 0 && stencil7_ok<T>(p.g);
-    const bool xdef = ctx().opt[8] != 0;
-    // z' = r*iD (:136) is not stored (wl_set_option(13), default on): the direction kernel recomputes it from r and iD
-    // (iD is a row constant away from the body), one array write + one read less per iteration; z keeps A*eps.
-    const bool zrec = ctx().opt[13] != 0;
-    // z = A*eps is not stored either (wl_set_option(19); 3-D vector kernels): the update kernel is a second 7-point kernel
+    if constexpr (D == 3) vec = pcg_vec_ok<T>(p.g);
+    const bool xdef = opt(WL_OPT_PCG_DEFER_X) != 0;
+    // z' = r*iD (:136) is not stored (WL_OPT_PCG_RECOMPUTE_PRECOND, default on): the direction kernel recomputes it from r
+    // and iD (iD is a row constant away from the body), one array write + one read less per iteration; z keeps A*eps.
+    const bool zrec = opt(WL_OPT_PCG_RECOMPUTE_PRECOND) != 0;
+    // z = A*eps is not stored either (pcg_recompute_aeps; 3-D vector kernels): the update kernel is a second 7-point kernel
     // over eps that forms the same A*eps again (same expression, same operands => same bits) and applies
     // r -= alpha*(A*eps) in its epilogue.  Per iteration one array write (mult) and one array read (update) are replaced
     // by a second read of eps (with its halo rows and planes).  Measured: 512^3 mult 0.303 -> 0.224 ms but update
     // 0.344 -> 0.449 ms (the 7-point form of the update runs at 4.1 TB/s): no gain; 256^3 as the finest level: -2.5 % per
     // step; levels of 128^3 cells and below are latency-bound and lose 5-10 % of a pcg! call to the heavier update kernel
-    // (tools/midlevels.py 19=3,0: 194 / 175, 110 / 101, 77 / 72 us).  Default (1): levels of 2^22 .. 2^26 cells; 3 = every
-    // level below 2^26; 2 = every level; 0 = never.
+    // (tools/midlevels.py PCG_RECOMPUTE_AEPS=3,0: 194 / 175, 110 / 101, 77 / 72 us).
     bool zst = false;
-    if constexpr (D == 3)
-        zst = (ctx().opt[19] == 2 || (ctx().opt[19] == 3 && R.count() < (1L << 26)) || (ctx().opt[19] == 1 && R.count() < (1L << 26) && R.count() >= (1L << 22))) &&
-              ctx().opt[5] != 0 && zrec && stencil7_ok<T>(p.g);
+    if constexpr (D == 3) zst = pcg_recompute_aeps(R.count()) && vec && zrec;
     // ---- how the dot products are finished (PcgDots above).  The in-kernel sums want few partials: the kernels of such a
-    // call cut z into at most `zcap` chunks (Gate::zcap); levels above 2^25 cells keep the finalize launches (option 15 = 1;
-    // 2 = never): there the cap costs the streaming kernels more than the launches it saves (512^3: +0.8 %).
+    // call cut z into at most `zcap` chunks (Gate::zcap); levels above 2^25 cells keep the finalize launches
+    // (pcg_dots_in_kernel): there the cap costs the streaming kernels more than the launches it saves (512^3: +0.8 %).
     const int tpp_v = D == 3 ? (((p.g.n[0] - 2 + 64 * VA::V - 1) / (64 * VA::V)) * ((p.g.n[1] - 2 + 3) / 4) + 7) / 8 * 8 : 0;
     const bool distr = p.g.dist && ctx().comm && ctx().comm->size > 1;
-    const bool gates = vec && xdef && zrec && R.count() > 0 && tpp_v > 0 &&
-                       (distr ? ctx().opt[15] != 0
-                              : ((ctx().opt[15] == 2 || (ctx().opt[15] == 1 && R.count() <= (1L << 25))) && tpp_v <= WL_PCG_PARTIALS));
+    const bool gates = vec && xdef && zrec && R.count() > 0 && tpp_v > 0 && pcg_dots_in_kernel(R.count(), distr) &&
+                       (distr || tpp_v <= WL_PCG_PARTIALS);
     const PcgForm form = !gates ? PcgForm::FINALIZE : (distr ? PcgForm::SLAB : PcgForm::IN_KERNEL);
     const int zcap = form == PcgForm::IN_KERNEL ? std::max(WL_PCG_PARTIALS / std::max(tpp_v, 1), 1) : 0;
     PcgDots<T> dots(form, st, partials, p.g.dist, xdef, want_r2, (T)10 * Lim<T>::eps, zcap);
@@ -1740,7 +1749,7 @@ int op_L2(const LevelT<T> &p, double *partials, State *st, bool after_pcg = fals
     int np = 0;
     int rcv = -1;
     if constexpr (D == 3) {
-        if (stencil7_ok<T>(p.g) && ctx().opt[5]) {   // 16-B streaming form; when the pcg! before it already produced r.r the
+        if (pcg_vec_ok<T>(p.g)) {   // 16-B streaming form; when the pcg! before it already produced r.r the
             using VA = VecA<T>;                      // gate closes and every workgroup leaves at once
             Gate gate;
             if (after_pcg) { gate.active = &st->r2_valid; gate.inv = 1; }

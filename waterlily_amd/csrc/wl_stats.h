@@ -208,7 +208,7 @@ inline int launch_meanflow(const G &g, const G &ga, const T *u, const T *p, A *U
     int tpp = 0, clen = 1, nchunk = 0;
     if (ntx > 0) {
         tpp = ((ntx * nty + 7) / 8) * 8;
-        chunking(tpp, g.n[2], 0, ctx().opt[17], &clen, &nchunk);
+        chunking(tpp, g.n[2], 0, opt(WL_OPT_STREAM_GRID_K), &clen, &nchunk);
     }
     const long nblk = (long)tpp * nchunk;
     const long nsc = (long)(g.n[0] - nv * V) * g.n[1] * g.n[2];       // i = 0 and the tail of every row

@@ -531,7 +531,7 @@ __global__ __launch_bounds__(256) void k_rowvec(G g, LD ld, ST st, const T *rowc
 // chunking of the marching axis: `tpp` workgroups per plane, `nown` planes; the grid is tpp*nchunk <= the target (also the
 // number of reduction partials); cap > 0 limits the number of chunks (in-kernel partial sums want few partials)
 inline void chunking(int tpp, int nown, int cap, int target_k, int *clen, int *nchunk) {
-    int target = target_k * 1024;                 // wl_set_option(16 / 17): grid size of the 7-point / streaming kernels in units of 1024 workgroups
+    int target = target_k * 1024;                 // WL_OPT_STENCIL7_GRID_K / WL_OPT_STREAM_GRID_K: grid size of the 7-point / streaming kernels in units of 1024 workgroups
     if (target < 1024) target = 1024;
     if (target > WL_MAXB) target = WL_MAXB;
     int want = target / tpp;
@@ -559,7 +559,7 @@ inline int launch_rowvec(int kclass, const G &g, LD ld, ST st, const T *rowc, do
     const int ntx = (g.n[0] - 2 + 64 * V - 1) / (64 * V), nty = (g.n[1] - 2 + 3) / 4;
     const int tpp = ((ntx * nty + 7) / 8) * 8;
     int clen, nchunk;
-    chunking(tpp, R.hi[2] - R.lo[2] + 1, gate.zcap, ctx().opt[17], &clen, &nchunk);
+    chunking(tpp, R.hi[2] - R.lo[2] + 1, gate.zcap, opt(WL_OPT_STREAM_GRID_K), &clen, &nchunk);
     const int nblk = tpp * nchunk;
     if (nblk > WL_MAXB) return -1;
     if (np) *np = nblk;
@@ -621,9 +621,11 @@ template <class T> inline int op_lrow(const G &g, const T *L, const T *iD, T *ro
 // can the vector kernels run on this level?  (any element-aligned pointers and any strides will do)
 template <class T> inline bool stencil7_ok(const G &g) {
     constexpr int V = Vec16<T>::V;
-    if (!ctx().opt[0]) return false;
+    if (!opt(WL_OPT_STENCIL7_VEC)) return false;
     return g.D == 3 && (g.n[0] - 2) % V == 0 && g.n[0] - 2 >= V;
 }
+// ... and the 16-B vector forms of the streaming kernels (pcg!, div, CFL, L2)?
+template <class T> inline bool pcg_vec_ok(const G &g) { return opt(WL_OPT_PCG_VEC) != 0 && stencil7_ok<T>(g); }
 
 // launch over the owned interior planes (or the plane sub-range [kov_lo,kov_hi]); *np = number of partials per reduced
 // value (0 if nothing to do).  Returns -1 when the level does not fit the launch (caller falls back).
@@ -639,7 +641,7 @@ inline int launch_stencil7_r(int kclass, const G &g, SRC src, const T *L, const 
     const int ntx = (g.n[0] - 2 + 64 * V - 1) / (64 * V), nty = (g.n[1] - 2 + S7_BY * R - 1) / (S7_BY * R);
     const int tpp = ((ntx * nty + 7) / 8) * 8;
     int clen, nchunk;
-    chunking(tpp, khi - klo + 1, gate.zcap, ctx().opt[16], &clen, &nchunk);
+    chunking(tpp, khi - klo + 1, gate.zcap, opt(WL_OPT_STENCIL7_GRID_K), &clen, &nchunk);
     const int nblk = tpp * nchunk;
     if (nblk > WL_MAXB) return -1;   // plane too large for the partial buffer: caller falls back
     if (np) *np = nblk;
@@ -649,13 +651,13 @@ inline int launch_stencil7_r(int kclass, const G &g, SRC src, const T *L, const 
                        partials, ntx, tpp, nblk, clen, klo, khi, gate);
     return (int)hipGetLastError();
 }
-// rows per thread: wl_set_option(4, .): 1 or 2 forced; 0 (default) = the source's preference (2 for array / Jacobi
+// rows per thread: WL_OPT_STENCIL7_ROWS: 1 or 2 forced; 0 (default) = the source's preference (2 for array / Jacobi
 // sources, 1 for the prolongation source) on levels of at least 2^26 interior cells whose y extent is even (half the
 // halo-row traffic; the larger register window costs occupancy, which only the big levels can afford to trade), else 1
 template <class T, int NRED, class SRC, class EPI>
 inline int launch_stencil7(int kclass, const G &g, SRC src, const T *L, const T *rowc, const T *ea, const T *eb, EPI epi,
                            double *partials, int *np, Gate gate = Gate(), int kov_lo = 0, int kov_hi = -1) {
-    const int want = ctx().opt[4];
+    const int want = opt(WL_OPT_STENCIL7_ROWS);
     const bool even = ((g.n[1] - 2) % 2) == 0;
     const bool two = even && (want == 2 || (want == 0 && SRC::ROWS_AUTO == 2 && r_inside(g).count() >= (1L << 26)));
     if (two) return launch_stencil7_r<T, NRED, 2>(kclass, g, src, L, rowc, ea, eb, epi, partials, np, gate, kov_lo, kov_hi);

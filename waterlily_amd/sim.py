@@ -25,7 +25,7 @@ import torch
 
 from . import _lib
 from . import body as B
-from ._lib import FlowDesc, Grid, LevelDesc, check, d3
+from ._lib import FlowDesc, Grid, LevelDesc, Opt, check, d3, get_option, opt_key, opt_name, options, set_option  # noqa: F401
 
 _TORCH = {np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64}
 _WLT = {np.dtype(np.float32): _lib.WL_F32, np.dtype(np.float64): _lib.WL_F64}
@@ -326,7 +326,7 @@ def accel_tuple(g, U, dt: Sequence[float], D: int):
 class Flow:
     """src/Flow.jl:92-122.  Fields: u, u0, f, V, mu0 (Ng...,D); mu1 (Ng...,D,D); p, sigma (Ng...).
     u0 is scratch between steps, as in the reference (mom_step! overwrites it before reading it, Flow.jl:154): after a step of a
-    3-D run without periodic directions / convective exit it holds the predictor's velocity, not the old one (wl_set_option(27))."""
+    3-D run without periodic directions / convective exit it holds the predictor's velocity, not the old one (Opt.BDIM_IN_CONVDIFF)."""
 
     def __init__(self, N, U, *, dt=0.25, nu=0.0, g=None, ulam=None, perdir=(), exitBC=False, T=np.float64,
                  device="cuda:0", padded=True, slab=None):
@@ -538,17 +538,6 @@ def uniform_rows(p, level=0):
     a, b = C.c_longlong(), C.c_longlong()
     check(_lib.lib().wl_mg_uniform_rows(p._h, int(level), C.byref(a), C.byref(b)))
     return a.value, b.value
-
-
-def set_option(key: int, value: int):
-    """Tuning / A-B switches of the library (include/wlhip.h, wl_set_option)."""
-    check(_lib.lib().wl_set_option(int(key), int(value)))
-
-
-def get_option(key: int) -> int:
-    v = C.c_int()
-    check(_lib.lib().wl_get_option(int(key), C.byref(v)))
-    return v.value
 
 
 def pcg(p, it=6, level=0) -> int:
