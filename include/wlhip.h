@@ -266,6 +266,41 @@ int wl_measure_fill(wl_flow *a, const wl_body_desc *body, double eps, int64_t *c
 /* nds(body, loc(0,I), t) = n * kern(clamp(d,-1,1))  (src/Metrics.jl:84-87, Float64) for n listed cells (indices as
  * written by wl_measure_fill): nds_dev[b*D + c] */
 int wl_body_nds(const wl_grid *g, const wl_body_desc *body, const int64_t *cand_dev, int64_t n, double *nds_dev);
+/* measure!(flow, body; t, eps) for a body given as a CLOSED TRIANGLE MESH (D == 3 only): the mesh twins of the three
+ * entry points above; everything they leave in the flow (sigma, the 15 coefficient arrays of touched-now-or-before rows,
+ * both BC! calls, halos, row flags, the changed-row record of wl_mg_update_changed, cand_dev ascending) is the same.
+ * The mesh lives in xi = A x + b with A a SIMILARITY (A A^T = s^2 I; anything else is refused), so distances in x are
+ * distances in xi divided by s.  Distance contract, in grid units of x, Float64:
+ *   exact zone: where the true unsigned distance is < exact_radius / s the value is the Euclidean distance to the closest
+ *               point c of the surface, signed by sign((xi - c) . n_pseudo), n_pseudo the angle-weighted pseudonormal of
+ *               the feature c lies on (face; sum of the two face normals on an edge; angle-weighted sum at a vertex --
+ *               Baerentzen & Aanaes 2005); the normal is (x - c)/d (n_pseudo/|n_pseudo| where |d| < 1e-9);
+ *               V = -A^-1 (dA/dt x + db/dt); normal and V are zero where d^2 exceeds the (2+eps)^2 of AutoBody.jl:118;
+ *   far zone  : elsewhere sigma only carries the right sign and |sigma| >= exact_radius / s; nothing downstream reads more
+ *               (src/Body.jl:35,44).
+ * wl_mesh_create (host only: no device is needed) checks its arguments -- nt == 0, indices out of range, non-finite
+ * coordinates, exact_radius <= 3 (it must reach 2 + eps + 1: the band test is made at cell centres, measure at faces half
+ * a cell away), degenerate triangles, an edge not shared by exactly two triangles, a shared edge traversed twice in the
+ * same direction -- then builds pseudonormals and a uniform bin grid (edge exact_radius/2) with per-bin triangle lists and
+ * inside/outside flags.  vert_host: nv x 3 doubles in xi space; tri_host: nt x 3 zero-based indices, outward by the
+ * right-hand rule.  The device copies are made by the first measure call that uses the handle (one allocation set; no
+ * later call allocates).  wl_mesh_info: out = {nt, nv, bins, max triangles per bin, sum of all bin lists, non-empty bins,
+ * device bytes, bins the surface crosses}.  wl_mesh_eval_host evaluates the same distance function the kernels use on
+ * the host (x_host: n x 3; d_host: n; n_host, V_host: n x 3 or NULL): d, normal and V with normal = V = 0 where
+ * d^2 > fastd2 -- for checking a mesh without a device. */
+typedef struct wl_mesh wl_mesh;
+typedef struct wl_mesh_pose {
+    double A[9], b[3], dA[9], db[3], Ainv[9];   /* row-major 3x3, as in wl_body_desc */
+    int32_t identity_map;                       /* != 0: xi = x, V = 0 */
+} wl_mesh_pose;
+int wl_mesh_create(wl_mesh **out, const double *vert_host, int64_t nv, const int32_t *tri_host, int64_t nt, double exact_radius);
+int wl_mesh_destroy(wl_mesh *m);
+int wl_mesh_info(const wl_mesh *m, int64_t out[8]);
+int wl_mesh_eval_host(const wl_mesh *m, const wl_mesh_pose *pose, const double *x_host, int64_t n, double fastd2, double *d_host,
+                      double *n_host, double *V_host);
+int wl_measure_rows_mesh(wl_flow *a, const wl_mesh *m, const wl_mesh_pose *pose, double eps, int64_t *nband);
+int wl_measure_fill_mesh(wl_flow *a, const wl_mesh *m, const wl_mesh_pose *pose, double eps, int64_t *cand_dev);
+int wl_body_nds_mesh(const wl_grid *g, const wl_mesh *m, const wl_mesh_pose *pose, const int64_t *cand_dev, int64_t n, double *nds_dev);
 /* project!(a,b,w)                     src/Flow.jl:137-145 */
 int wl_project(wl_flow *a, wl_mg *b, double dt, double w, int *n_iter);
 /* mom_step!(a,b)                      src/Flow.jl:153-169.  dt = a.dt[end]; U = BCTuple(a.U,a.dt,N);

@@ -46,6 +46,12 @@ class BodyDesc(C.Structure):
                 ("op", C.c_int32), ("count", C.c_int32)]
 
 
+class MeshPose(C.Structure):
+    """wl_mesh_pose (include/wlhip.h): the affine map of a mesh body at one instant"""
+    _fields_ = [("A", C.c_double * 9), ("b", C.c_double * 3), ("dA", C.c_double * 9), ("db", C.c_double * 3),
+                ("Ainv", C.c_double * 9), ("identity_map", C.c_int32)]
+
+
 WL_BODY_SPHERE, WL_BODY_TORUS, WL_BODY_PLATE, WL_BODY_CYLINDER = 0, 1, 2, 3
 WL_BODY_OP_UNION, WL_BODY_OP_MINUS, WL_BODY_OP_INTERSECT = 0, 1, 2
 WL_BODY_MAXLEAF = 6
@@ -195,6 +201,13 @@ def lib() -> C.CDLL:
         "wl_measure_rows": (i, [vp, C.POINTER(BodyDesc), d, C.POINTER(i64)]),
         "wl_measure_fill": (i, [vp, C.POINTER(BodyDesc), d, vp]),
         "wl_body_nds": (i, [gp, C.POINTER(BodyDesc), vp, i64, vp]),
+        "wl_mesh_create": (i, [C.POINTER(vp), vp, i64, vp, i64, d]),
+        "wl_mesh_destroy": (i, [vp]),
+        "wl_mesh_info": (i, [vp, C.POINTER(i64)]),
+        "wl_mesh_eval_host": (i, [vp, C.POINTER(MeshPose), vp, i64, d, vp, vp, vp]),
+        "wl_measure_rows_mesh": (i, [vp, vp, C.POINTER(MeshPose), d, C.POINTER(i64)]),
+        "wl_measure_fill_mesh": (i, [vp, vp, C.POINTER(MeshPose), d, vp]),
+        "wl_body_nds_mesh": (i, [gp, vp, C.POINTER(MeshPose), vp, i64, vp]),
         "wl_project": (i, [vp, vp, d, d, ip]),
         "wl_mom_step": (i, [vp, vp, d, dp, dp, dp, dp, ip]),
         "wl_metric": (i, [i, gp, i, vp, vp, i, dp, dp]),

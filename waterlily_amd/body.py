@@ -19,7 +19,7 @@ from typing import Callable, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-__all__ = ["AutoBody", "NoBody", "Sphere", "Torus", "AffineMap", "translation", "rotation2d", "measure", "sdf", "kern",
+__all__ = ["AutoBody", "NoBody", "Sphere", "Torus", "AffineMap", "translation", "rotation2d", "rotation3d", "scaled", "measure", "sdf", "kern",
            "kern0", "kern1", "mu0", "mu1", "norm2", "measure_fields", "measure_fields_into", "nds_band"]
 
 
@@ -127,6 +127,68 @@ def rotation2d(center, w, th0=0.0) -> AffineMap:
     return _Rotation2D(center, w, th0)
 
 
+class _Rotation3D(AffineMap):
+    """xi = R(theta) (x - c), theta = w t + th0, R the rotation by -theta about the unit `axis` (Rodrigues:
+    R = I - sin(theta) K + (1 - cos(theta)) K^2, K the cross-product matrix of the axis): the body turns by +theta about the
+    axis through c, the 3-D sibling of rotation2d."""
+
+    def __init__(self, center, axis, w, th0=0.0):
+        self.c = np.broadcast_to(np.asarray(center, dtype=np.float64), (3,)).copy()
+        k = np.asarray(axis, dtype=np.float64).reshape(3)
+        if not np.linalg.norm(k) > 0:
+            raise ValueError("rotation3d: the axis must not be zero")
+        k = k / np.linalg.norm(k)
+        self.K = np.array([[0.0, -k[2], k[1]], [k[2], 0.0, -k[0]], [-k[1], k[0], 0.0]])
+        self.K2 = self.K @ self.K
+        self.w, self.th0 = float(w), float(th0)
+
+    def _R(self, t):
+        s, c = math.sin(self.w * t + self.th0), math.cos(self.w * t + self.th0)
+        return np.eye(3) - s * self.K + (1 - c) * self.K2, (-c * self.K + s * self.K2) * self.w
+
+    def coeffs(self, t):
+        R, dR = self._R(t)
+        return R, -R @ self.c, dR, -dR @ self.c
+
+    def inverse(self, t):
+        """A^-1 = R^T (analytic)"""
+        return self._R(t)[0].T
+
+    def __call__(self, x, t):
+        th = self.w * t + self.th0
+        s, c = torch.sin(th), torch.cos(th)
+        K = torch.as_tensor(self.K, dtype=x.dtype, device=x.device)
+        K2 = torch.as_tensor(self.K2, dtype=x.dtype, device=x.device)
+        R = torch.eye(3, dtype=x.dtype, device=x.device) - s * K + (1 - c) * K2
+        return R @ (x - torch.as_tensor(self.c, dtype=x.dtype, device=x.device)[:, None])
+
+
+def rotation3d(center, axis, w, th0=0.0) -> AffineMap:
+    return _Rotation3D(center, axis, w, th0)
+
+
+class _Scaled(AffineMap):
+    """xi = s * inner(x, t): a uniform scaling after another affine map (a body 1/s times the size)"""
+
+    def __init__(self, inner: AffineMap, s: float):
+        self.inner, self.s = inner, float(s)
+
+    def coeffs(self, t):
+        A, b, dA, db = self.inner.coeffs(t)
+        return self.s * A, self.s * b, self.s * dA, self.s * db
+
+    def inverse(self, t):
+        inv = getattr(self.inner, "inverse", None)
+        return (inv(t) if inv is not None else np.linalg.inv(self.inner.coeffs(t)[0])) / self.s
+
+    def __call__(self, x, t):
+        return self.s * self.inner(x, t)
+
+
+def scaled(inner: AffineMap, s: float) -> AffineMap:
+    return _Scaled(inner, s)
+
+
 class ParametricBody(AutoBody):
     """An AutoBody whose sdf is one of the library's closed-form families and whose map (if any) is affine: besides the
     torch closures (generic path: host geometry, other back ends) it can describe itself to the HIP `measure!` kernel."""
@@ -232,9 +294,11 @@ class Bodies(AutoBody):
 
 
 def is_native(body) -> bool:
-    """can the HIP measure! kernels take this body? (a parametric leaf or a composite of at most WL_BODY_MAXLEAF of them)"""
+    """can the HIP measure! kernels take this body? (a parametric leaf, a composite of at most WL_BODY_MAXLEAF of them, or a
+    triangle mesh)"""
     from ._lib import WL_BODY_MAXLEAF
-    return isinstance(body, ParametricBody) or (isinstance(body, Bodies) and len(body.bodies) <= WL_BODY_MAXLEAF)
+    from .mesh import MeshBody
+    return isinstance(body, (ParametricBody, MeshBody)) or (isinstance(body, Bodies) and len(body.bodies) <= WL_BODY_MAXLEAF)
 
 
 class Sphere(ParametricBody):

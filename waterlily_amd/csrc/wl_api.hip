@@ -12,6 +12,7 @@
 #include "wl_ops.h"
 #include "wl_coarse.h"
 #include "wl_measure.h"
+#include "wl_mesh.h"
 #include "wl_stats.h"
 #include "wl_probe.h"
 #include "wl_integrals.h"
@@ -736,16 +737,17 @@ static int measure_alloc(wl_flow *a, size_t nrows) {
     WL_HIP(wl_dev_alloc((void **)&a->changed, nrows));
     return 0;
 }
-template <class T, int D> static int measure_rows(wl_flow *a, const wl_body_desc *body, double eps, int64_t *nband) {
+// The two halves of a native measure! with the body's own kernels passed in: `rows(g, nrows, d2)` launches the sigma / band
+// count / touched-flag kernel, `fill(g, nrows, d2, cand)` the coefficient / band-list kernel (parametric: wl_measure.h;
+// triangle mesh: wl_mesh.h).  Everything around them does not know what shape the body has.
+template <class T, int D, class Rows> static int measure_rows_with(wl_flow *a, double eps, int64_t *nband, Rows rows) {
     const G g = mkG(&a->d.g);
     const size_t nrows = (size_t)g.n[1] * (size_t)(D > 2 ? g.n[2] : 1);
     WL_TRY(measure_alloc(a, nrows));
-    const BodyDev B = body_dev(body);
     const T d2 = (T)((2 + eps) * (2 + eps));
     {
         Prof p(WL_K_MISC, g.cells());
-        hipLaunchKernelGGL((k_measure_rows<T, D>), dim3((unsigned)((nrows + 3) / 4)), dim3(256), 0, ctx().stream, g, B, (T *)a->d.sigma, d2,
-                           a->rowcount, a->touched);
+        rows(g, nrows, d2);
         WL_HIP(hipGetLastError());
         hipLaunchKernelGGL(k_scan_rows, dim3(1), dim3(1024), 0, ctx().stream, (const int *)a->rowcount, a->rowoff, (long)nrows);
         WL_HIP(hipGetLastError());
@@ -757,16 +759,19 @@ template <class T, int D> static int measure_rows(wl_flow *a, const wl_body_desc
     *nband = tot;
     return 0;
 }
-template <class T, int D> static int measure_fill(wl_flow *a, const wl_body_desc *body, double eps, int64_t *cand) {
+template <class T, int D> static int measure_rows(wl_flow *a, const wl_body_desc *body, double eps, int64_t *nband) {
+    const BodyDev B = body_dev(body);
+    return measure_rows_with<T, D>(a, eps, nband, [&](const G &g, size_t nrows, T d2) {
+        hipLaunchKernelGGL((k_measure_rows<T, D>), dim3((unsigned)((nrows + 3) / 4)), dim3(256), 0, ctx().stream, g, B, (T *)a->d.sigma, d2,
+                           a->rowcount, a->touched);
+    });
+}
+template <class T, int D, class Fill> static int measure_fill_with(wl_flow *a, int64_t *cand, Fill fill) {
     const G g = mkG(&a->d.g);
     const size_t nrows = (size_t)g.n[1] * (size_t)(D > 2 ? g.n[2] : 1);
-    const BodyDev B = body_dev(body);
-    const T d2 = (T)((2 + eps) * (2 + eps));
     {
         Prof p(WL_K_MISC, g.cells());
-        hipLaunchKernelGGL((k_measure_fill<T, D>), dim3((unsigned)((nrows + 3) / 4)), dim3(256), 0, ctx().stream, g, B, (const T *)a->d.sigma, d2,
-                           (2 + eps) * (2 + eps), eps, (T *)a->d.mu0, (T *)a->d.mu1, (T *)a->d.V, (const unsigned char *)a->touched,
-                           (const unsigned char *)a->prev, !a->prev_valid, (const long *)a->rowoff, (long *)cand);
+        fill(g, nrows, cand);
         WL_HIP(hipGetLastError());
     }
     a->nband = -1;
@@ -789,6 +794,91 @@ template <class T, int D> static int measure_fill(wl_flow *a, const wl_body_desc
     WL_TRY(flow_compact_busy(a, g, D));
     a->prev_valid = true;
     return 0;
+}
+template <class T, int D> static int measure_fill(wl_flow *a, const wl_body_desc *body, double eps, int64_t *cand) {
+    const BodyDev B = body_dev(body);
+    const T d2 = (T)((2 + eps) * (2 + eps));
+    return measure_fill_with<T, D>(a, cand, [&](const G &g, size_t nrows, int64_t *cd) {
+        hipLaunchKernelGGL((k_measure_fill<T, D>), dim3((unsigned)((nrows + 3) / 4)), dim3(256), 0, ctx().stream, g, B, (const T *)a->d.sigma, d2,
+                           (2 + eps) * (2 + eps), eps, (T *)a->d.mu0, (T *)a->d.mu1, (T *)a->d.V, (const unsigned char *)a->touched,
+                           (const unsigned char *)a->prev, !a->prev_valid, (const long *)a->rowoff, (long *)cd);
+    });
+}
+// ---- triangle-mesh bodies (wl_mesh.h)
+static int mesh_upload(const wl_mesh *m) {
+    if (m->d_tri) return 0;
+    // the handle's pointers are set only once all four copies are on the device: a failure part-way frees what it made and
+    // leaves the handle as it was (not uploaded), so a later call starts again instead of launching with half the arrays
+    double *tri = nullptr;
+    int *start = nullptr, *list = nullptr;
+    signed char *sign = nullptr;
+    const size_t nlist = std::max<size_t>(m->bin_tri.size(), 1);
+    hipError_t e = wl_dev_alloc((void **)&tri, m->tri.size() * sizeof(double));
+    if (e == hipSuccess) e = wl_dev_alloc((void **)&start, m->bin_start.size() * sizeof(int));
+    if (e == hipSuccess) e = wl_dev_alloc((void **)&list, nlist * sizeof(int));
+    if (e == hipSuccess) e = wl_dev_alloc((void **)&sign, m->bin_sign.size());
+    if (e == hipSuccess) e = hipMemcpyAsync(tri, m->tri.data(), m->tri.size() * sizeof(double), hipMemcpyHostToDevice, ctx().stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(start, m->bin_start.data(), m->bin_start.size() * sizeof(int), hipMemcpyHostToDevice, ctx().stream);
+    if (e == hipSuccess && !m->bin_tri.empty())
+        e = hipMemcpyAsync(list, m->bin_tri.data(), m->bin_tri.size() * sizeof(int), hipMemcpyHostToDevice, ctx().stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(sign, m->bin_sign.data(), m->bin_sign.size(), hipMemcpyHostToDevice, ctx().stream);
+    const hipError_t es = hipStreamSynchronize(ctx().stream);   // (also on failure: no copy may still be reading the host arrays)
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) {
+        if (tri) (void)hipFree(tri);
+        if (start) (void)hipFree(start);
+        if (list) (void)hipFree(list);
+        if (sign) (void)hipFree(sign);
+        return fail((int)e, "uploading the mesh bins", __FILE__, __LINE__);
+    }
+    m->d_start = start; m->d_list = list; m->d_sign = sign; m->d_tri = tri;
+    return 0;
+}
+// the pose as the kernels take it; refuses a map that is not a similarity (A A^T = s^2 I) or whose exact zone R/s is too thin
+static int mesh_pose(const wl_mesh *m, const wl_mesh_pose *p, double need, PoseDev &o) {
+    if (!m || !p) return fail(WL_E_ARG, "null mesh or pose", __FILE__, __LINE__);
+    o.ident = p->identity_map != 0;
+    o.s = 1.0;
+    for (int q = 0; q < 9; ++q) { o.A[q] = p->A[q]; o.dA[q] = p->dA[q]; o.Ainv[q] = p->Ainv[q]; }
+    for (int q = 0; q < 3; ++q) { o.b[q] = p->b[q]; o.db[q] = p->db[q]; }
+    if (!o.ident) {
+        double gm[9], s2 = 0;
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 3; ++c) {
+                double s = 0;
+                for (int q = 0; q < 3; ++q) s += p->A[3 * r + q] * p->A[3 * c + q];
+                gm[3 * r + c] = s;
+            }
+        s2 = (gm[0] + gm[4] + gm[8]) / 3;
+        if (!(s2 > 0) || !std::isfinite(s2)) return fail(WL_E_ARG, "mesh pose: the map is singular", __FILE__, __LINE__);
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 3; ++c)
+                if (std::fabs(gm[3 * r + c] - (r == c ? s2 : 0.0)) > 1e-10 * s2)
+                    return fail(WL_E_ARG, "mesh pose: the map is not a similarity (A A^T != s^2 I)", __FILE__, __LINE__);
+        o.s = std::sqrt(s2);
+    }
+    // (a relative 1e-9 of slack: the caller computes s on its own, and a rotating map's s wanders by an ulp from step to step;
+    //  `need` itself carries half a cell more than the faces, the farthest points measured, can be away)
+    if (m->R < need * o.s * (1.0 - 1e-9)) return fail(WL_E_ARG, "mesh pose: exact_radius too small for this eps and map scale (needs (2 + eps + 1) * s)", __FILE__, __LINE__);
+    return 0;
+}
+template <class T> static int mesh_rows(wl_flow *a, const wl_mesh *m, const PoseDev &P, double eps, int64_t *nband) {
+    WL_TRY(mesh_upload(m));
+    const MeshDev M = m->view(true);
+    return measure_rows_with<T, 3>(a, eps, nband, [&](const G &g, size_t nrows, T d2) {
+        hipLaunchKernelGGL((k_mesh_rows<T>), dim3((unsigned)((nrows + 3) / 4)), dim3(256), 0, ctx().stream, g, M, P, (T *)a->d.sigma, d2,
+                           a->rowcount, a->touched);
+    });
+}
+template <class T> static int mesh_fill(wl_flow *a, const wl_mesh *m, const PoseDev &P, double eps, int64_t *cand) {
+    WL_TRY(mesh_upload(m));
+    const MeshDev M = m->view(true);
+    const T d2 = (T)((2 + eps) * (2 + eps));
+    return measure_fill_with<T, 3>(a, cand, [&](const G &g, size_t nrows, int64_t *cd) {
+        hipLaunchKernelGGL((k_mesh_fill<T>), dim3((unsigned)((nrows + 3) / 4)), dim3(256), 0, ctx().stream, g, M, P, (const T *)a->d.sigma, d2,
+                           (2 + eps) * (2 + eps), eps, (T *)a->d.mu0, (T *)a->d.mu1, (T *)a->d.V, (const unsigned char *)a->touched,
+                           (const unsigned char *)a->prev, !a->prev_valid, (const long *)a->rowoff, (long *)cd);
+    });
 }
 static int check_body(const wl_body_desc *b, int D) {
     if (!b) return fail(WL_E_ARG, "null body", __FILE__, __LINE__);
@@ -1355,6 +1445,84 @@ int wl_body_nds(const wl_grid *g, const wl_body_desc *body, const int64_t *cand_
     Prof p(WL_K_PFORCE, n);
     if (g->D == 3) hipLaunchKernelGGL((k_body_nds<3>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx().stream, gg, B, (const long *)cand_dev, (long)n, nds_dev);
     else hipLaunchKernelGGL((k_body_nds<2>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx().stream, gg, B, (const long *)cand_dev, (long)n, nds_dev);
+    return (int)hipGetLastError();
+}
+int wl_mesh_create(wl_mesh **out, const double *vert_host, int64_t nv, const int32_t *tri_host, int64_t nt, double exact_radius) {
+    if (!out || !vert_host || !tri_host) return fail(WL_E_ARG, "wl_mesh_create: null argument", __FILE__, __LINE__);
+    if (nt <= 0 || nv <= 0) return fail(WL_E_ARG, "wl_mesh_create: empty mesh (nt == 0 or nv == 0)", __FILE__, __LINE__);
+    if (nt > (int64_t)0x3fffffff || nv > (int64_t)0x7fffffff) return fail(WL_E_ARG, "wl_mesh_create: mesh too large", __FILE__, __LINE__);
+    if (!(exact_radius > 3.0) || !std::isfinite(exact_radius))
+        return fail(WL_E_ARG, "wl_mesh_create: exact_radius too small (needs 2 + eps + 1 with eps > 0)", __FILE__, __LINE__);
+    wl_mesh *m = new wl_mesh;
+    const char *err = mesh_build(*m, vert_host, nv, tri_host, nt, exact_radius);
+    if (err) { delete m; return fail(WL_E_ARG, err, __FILE__, __LINE__); }
+    *out = m;
+    return 0;
+}
+int wl_mesh_destroy(wl_mesh *m) {
+    if (!m) return 0;
+    if (m->d_tri) {
+        (void)hipStreamSynchronize(ctx().stream);
+        (void)hipFree(m->d_tri); (void)hipFree(m->d_start); (void)hipFree(m->d_list); (void)hipFree(m->d_sign);
+    }
+    delete m;
+    return 0;
+}
+int wl_mesh_info(const wl_mesh *m, int64_t out[8]) {
+    if (!m || !out) return fail(WL_E_ARG, "wl_mesh_info: null argument", __FILE__, __LINE__);
+    out[0] = m->nt; out[1] = m->nv; out[2] = (int64_t)m->bin_sign.size(); out[3] = m->max_per_bin;
+    out[4] = (int64_t)m->bin_tri.size(); out[5] = m->nonempty; out[6] = (int64_t)m->device_bytes(); out[7] = m->crossed;
+    return 0;
+}
+int wl_mesh_eval_host(const wl_mesh *m, const wl_mesh_pose *pose, const double *x_host, int64_t n, double fastd2, double *d_host,
+                      double *n_host, double *V_host) {
+    PoseDev P;
+    WL_TRY(mesh_pose(m, pose, 0.0, P));
+    if (n > 0 && (!x_host || !d_host)) return fail(WL_E_ARG, "wl_mesh_eval_host: null buffer", __FILE__, __LINE__);
+    const MeshDev M = m->view(false);
+    for (int64_t q = 0; q < n; ++q) {
+        const double x[3] = {x_host[3 * q], x_host[3 * q + 1], x_host[3 * q + 2]};
+        double nn[3], V[3];
+        mesh_measure(M, P, x, fastd2, d_host[q], nn, V);
+        for (int c = 0; c < 3; ++c) {
+            if (n_host) n_host[3 * q + c] = nn[c];
+            if (V_host) V_host[3 * q + c] = V[c];
+        }
+    }
+    return 0;
+}
+int wl_measure_rows_mesh(wl_flow *a, const wl_mesh *m, const wl_mesh_pose *pose, double eps, int64_t *nband) {
+    if (!a || !nband) return fail(WL_E_ARG, "wl_measure_rows_mesh: null argument", __FILE__, __LINE__);
+    if (a->d.g.D != 3) return fail(WL_E_ARG, "wl_measure_rows_mesh: a triangle mesh needs D == 3", __FILE__, __LINE__);
+    if (!(eps > 0)) return fail(WL_E_ARG, "wl_measure_rows_mesh: eps must be positive", __FILE__, __LINE__);
+    PoseDev P;
+    WL_TRY(mesh_pose(m, pose, 2 + eps + 1, P));
+    if (a->t == WL_F32) return mesh_rows<float>(a, m, P, eps, nband);
+    return mesh_rows<double>(a, m, P, eps, nband);
+}
+int wl_measure_fill_mesh(wl_flow *a, const wl_mesh *m, const wl_mesh_pose *pose, double eps, int64_t *cand_dev) {
+    if (!a) return fail(WL_E_ARG, "null handle", __FILE__, __LINE__);
+    if (a->d.g.D != 3) return fail(WL_E_ARG, "wl_measure_fill_mesh: a triangle mesh needs D == 3", __FILE__, __LINE__);
+    if (!(eps > 0)) return fail(WL_E_ARG, "wl_measure_fill_mesh: eps must be positive", __FILE__, __LINE__);
+    PoseDev P;
+    WL_TRY(mesh_pose(m, pose, 2 + eps + 1, P));
+    if (a->nband < 0) return fail(WL_E_STATE, "wl_measure_fill_mesh: call wl_measure_rows_mesh first", __FILE__, __LINE__);
+    if (a->nband > 0 && !cand_dev) return fail(WL_E_ARG, "wl_measure_fill_mesh: null candidate buffer", __FILE__, __LINE__);
+    if (a->t == WL_F32) return mesh_fill<float>(a, m, P, eps, cand_dev);
+    return mesh_fill<double>(a, m, P, eps, cand_dev);
+}
+int wl_body_nds_mesh(const wl_grid *g, const wl_mesh *m, const wl_mesh_pose *pose, const int64_t *cand_dev, int64_t n, double *nds_dev) {
+    WL_TRY(check_grid(g));
+    if (g->D != 3) return fail(WL_E_ARG, "wl_body_nds_mesh: a triangle mesh needs D == 3", __FILE__, __LINE__);
+    PoseDev P;
+    WL_TRY(mesh_pose(m, pose, 1.0, P));
+    if (n <= 0) return 0;
+    if (!cand_dev || !nds_dev) return fail(WL_E_ARG, "wl_body_nds_mesh: null buffer", __FILE__, __LINE__);
+    WL_TRY(mesh_upload(m));
+    const G gg = mkG(g);
+    const MeshDev M = m->view(true);
+    Prof p(WL_K_PFORCE, n);
+    hipLaunchKernelGGL(k_mesh_nds, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx().stream, gg, M, P, (const long *)cand_dev, (long)n, nds_dev);
     return (int)hipGetLastError();
 }
 static int check_pair(const wl_flow *a, const wl_mg *b) {

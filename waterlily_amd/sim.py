@@ -25,6 +25,7 @@ import torch
 
 from . import _lib
 from . import body as B
+from .mesh import MeshBody
 from ._lib import FlowDesc, Grid, LevelDesc, Opt, check, d3, get_option, opt_key, opt_name, options, set_option  # noqa: F401
 
 _TORCH = {np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64}
@@ -683,15 +684,25 @@ def measure_flow(a: Flow, body, t=0.0, eps=1, geometry="device") -> None:
         return
     dims = tuple(n - 2 for n in a.N)
     a._band_cells = None
+    if isinstance(body, MeshBody) and (geometry != "device" or a.D != 3):
+        raise ValueError('a MeshBody is measured by the HIP kernels only: it needs geometry="device" and a 3-D grid '
+                         f'(got geometry={geometry!r}, D={a.D})')
     if geometry == "device" and B.is_native(body):
-        # closed-form family + affine map: the whole measure! (fill loop, both BC! calls, halos, row flags) runs as
-        # hand-written kernels (csrc/wl_measure.h); only rows holding body cells now or before are rewritten
+        # closed-form family + affine map, or a triangle mesh: the whole measure! (fill loop, both BC! calls, halos, row
+        # flags) runs as hand-written kernels (csrc/wl_measure.h, wl_mesh.h); only rows holding body cells now or before
+        # are rewritten
         L = _lib.lib()
-        desc = body.native_desc(t, a.D)
         nband = C.c_int64()
-        check(L.wl_measure_rows(a._h, desc, float(eps), C.byref(nband)))
-        cand = torch.empty(max(1, nband.value), dtype=torch.int64, device=a.device)
-        check(L.wl_measure_fill(a._h, desc, float(eps), C.c_void_p(cand.data_ptr())))
+        if isinstance(body, MeshBody):
+            h, pose = body.native(t, eps)
+            check(L.wl_measure_rows_mesh(a._h, h, C.byref(pose), float(eps), C.byref(nband)))
+            cand = torch.empty(max(1, nband.value), dtype=torch.int64, device=a.device)
+            check(L.wl_measure_fill_mesh(a._h, h, C.byref(pose), float(eps), C.c_void_p(cand.data_ptr())))
+        else:
+            desc = body.native_desc(t, a.D)
+            check(L.wl_measure_rows(a._h, desc, float(eps), C.byref(nband)))
+            cand = torch.empty(max(1, nband.value), dtype=torch.int64, device=a.device)
+            check(L.wl_measure_fill(a._h, desc, float(eps), C.c_void_p(cand.data_ptr())))
         a._band_cells = (float(t), cand[:nband.value])
         return
     if geometry == "device":
@@ -837,10 +848,15 @@ def _ensure_band(sim: Simulation) -> None:
             kk = cand // int(sim.flow.N[0] * sim.flow.N[1])
             sl = sim.slab
             cand = cand[(kk >= sl.own_lo) & (kk <= sl.own_hi) & (kk + sl.kz0 >= 1) & (kk + sl.kz0 <= sim.flow.N[2] - 2)]
-        desc = sim.body.native_desc(t, sim.flow.D)
         nds = torch.empty((cand.numel(), sim.flow.D), dtype=torch.float64, device=cand.device)
         g = _grid_of(sim.flow.p, sim.flow.D)
-        check(_lib.lib().wl_body_nds(C.byref(g), desc, C.c_void_p(cand.data_ptr()), cand.numel(), C.c_void_p(nds.data_ptr())))
+        if isinstance(sim.body, MeshBody):
+            h, pose = sim.body.native(t, sim.eps)
+            check(_lib.lib().wl_body_nds_mesh(C.byref(g), h, C.byref(pose), C.c_void_p(cand.data_ptr()), cand.numel(),
+                                              C.c_void_p(nds.data_ptr())))
+        else:
+            desc = sim.body.native_desc(t, sim.flow.D)
+            check(_lib.lib().wl_body_nds(C.byref(g), desc, C.c_void_p(cand.data_ptr()), cand.numel(), C.c_void_p(nds.data_ptr())))
         keep = (nds != 0).any(1)
         sim._band = (t,) + band_to_device_t(sim.flow.p, cand[keep], nds[keep])
         return
