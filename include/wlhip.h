@@ -388,7 +388,35 @@ int wl_interp(wl_dtype t, const wl_grid *g, const void *a, int ncomp, const doub
  * (dead) and is skipped from then on.  dt finite and >= 0.  A z-slab grid is refused (WL_E_STATE).  Asynchronous. */
 int wl_tracer_advance(wl_dtype t, const wl_grid *g, const void *u, double *x_dev, int64_t m, double dt, int perdir_mask);
 
-/* ------------------------------------------------------------------ snapshots (VTK write / restart, ext/WaterLilyWriteVTKExt.jl:57-66,
+/* ------------------------------------------------------------------ surface loads of a mesh body (SurfaceLoads, waterlily_amd/surface.py)
+ * Pressure and viscous traction PER TRIANGLE of a wl_mesh at the pose of one instant (D == 3), all in double for either T:
+ *   x_v = Ainv (xi_v - b) (x_v = xi_v when identity_map);  x_c = (x_a + x_b + x_c) / 3;  S = (x_b - x_a) x (x_c - x_a) / 2
+ *   (area times the outward normal, grid units of x);  n = S / |S|;  V_b = -Ainv (dA x_c + db) (0 for the identity map)
+ * and at the sample point x_c + delta n, in index coordinates X = x_c + delta n + 1.5 (wl_interp's convention):
+ *   p_t = interp(X, p);   G_ij = u_i(X + e_j/2) - u_i(X - e_j/2), u_i sampled as wl_interp samples component i (at + e_i/2);
+ *   tau_i = -nu sum_j (G_ij + G_ji) n_j      (the integrand of viscous_force, src/Metrics.jl:116-119)
+ * p_t S is the triangle's pressure load and tau |S| its viscous load, with the signs of wl_pforce / wl_vforce.
+ * rows_dev: nt*4 doubles {p_t, tau_x, tau_y, tau_z}; geom_dev: nt*9 doubles {x_c, S, V_b}, or NULL.  A sample with a weighted
+ * corner outside the array gives NaN in that triangle's entries only (wl_interp's rule).  z-slabs: each of the 19 interp
+ * entries of a triangle follows wl_interp's ownership rule (the owner contributes the value, every other rank 0), so every rank
+ * writes a PARTIAL row and the sum over the ranks is the value; geometry rows are the same on every rank.
+ * mean_dev (nt*4 doubles, or NULL): the running mean of the row, m <- m + w (v - m), w in (0, 1] computed by the host as
+ * wl_meanflow_update's eps is; first != 0: m = v, and m is not read.  Linear too: slab partials sum.
+ * Refused with WL_E_ARG before the device is touched: NULL mesh, pose or rows_dev; D != 3; delta negative or not finite; nu not
+ * finite; a pose that is not a similarity.  Asynchronous: one launch on the library's stream; nothing is allocated unless this
+ * is the first call that uses the mesh handle on the device (it then makes the device copies, as wl_measure_rows_mesh does).
+ *
+ * wl_surface_totals reduces such rows to out_dev[12] (device memory) about the point x0:
+ *   Fp = sum p_t S;  Fv = sum tau |S|;  Mp = sum (x_c - x0) x p_t S;  Mv = sum (x_c - x0) x tau |S|
+ * in a fixed order (per thread in ascending triangle order, wavefront, workgroup, one final workgroup; no floating-point
+ * atomics: the same rows give the same bits); a NaN row makes the sums it enters NaN.  On z-slabs the totals of partial rows are
+ * partial totals.  Asynchronous: two launches, nothing allocated after the library's first reduction.  WaterLily v1.3 has no
+ * such functions to override: the entry points are there for a later binding. */
+int wl_surface_sample(wl_dtype t, const wl_grid *g, const void *p, const void *u, const wl_mesh *m, const wl_mesh_pose *pose,
+                      double delta, double nu, double *rows_dev, double *geom_dev, double *mean_dev, double w, int first);
+int wl_surface_totals(const double *rows_dev, const double *geom_dev, int64_t nt, const double x0[3], double *out_dev);
+
+/* ------------------------------------------------------------------ snapshots (VTK write / restart,ext/WaterLilyWriteVTKExt.jl:57-66,
  * ext/WaterLilyReadVTKExt.jl:28-45).  The reference copies whole fields to the host (`a.flow.u |> Array`) and permutes the vector
  * components to the front there (components_first, :79).  Here the field's LOCAL planes klo..khi are packed on the device into
  * a dense array-of-tuples staging buffer -- dst[((kk*n1 + j)*n0 + i)*ntuple + c] = a_c[i, j, klo+kk] for c < ncomp, 0 for the

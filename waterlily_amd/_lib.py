@@ -218,6 +218,8 @@ def lib() -> C.CDLL:
         "wl_meanflow_update": (i, [i, i, gp, vp, vp, gp, vp, vp, vp, vp, d, i]),
         "wl_interp": (i, [i, gp, vp, i, vp, i64, vp, i64]),
         "wl_tracer_advance": (i, [i, gp, vp, vp, i64, d, i]),
+        "wl_surface_sample": (i, [i, gp, vp, vp, vp, C.POINTER(MeshPose), d, d, vp, vp, vp, d, i]),
+        "wl_surface_totals": (i, [vp, vp, i64, dp, vp]),
         "wl_snapshot_pack": (i, [i, gp, vp, i, i, i, i, vp]),
         "wl_snapshot_unpack": (i, [i, gp, vp, i, i, i, i, vp]),
         "wl_set_option": (i, [i, i]),

@@ -16,6 +16,7 @@
 #include "wl_stats.h"
 #include "wl_probe.h"
 #include "wl_integrals.h"
+#include "wl_surface.h"
 
 namespace wl {
 
@@ -1615,6 +1616,35 @@ int wl_interp(wl_dtype t, const wl_grid *g, const void *a, int ncomp, const doub
     if (ldo < (ncomp > 1 ? ncomp : 1)) return fail(WL_E_ARG, "wl_interp: ldo smaller than one row of the result", __FILE__, __LINE__);
     const G gg = mkG(g);
     WL_DISPATCH(t, g->D, (op_interp<T, DD>(gg, (const T *)a, ncomp, x_dev, m, out_dev, ldo)));
+}
+int wl_surface_sample(wl_dtype t, const wl_grid *g, const void *p, const void *u, const wl_mesh *m, const wl_mesh_pose *pose,
+                      double delta, double nu, double *rows_dev, double *geom_dev, double *mean_dev, double w, int first) {
+    if (!m || !pose) return fail(WL_E_ARG, "wl_surface_sample: null mesh or pose", __FILE__, __LINE__);
+    if (!rows_dev) return fail(WL_E_ARG, "wl_surface_sample: null output rows", __FILE__, __LINE__);
+    WL_TRY(check_grid(g));
+    if (g->D != 3) return fail(WL_E_ARG, "wl_surface_sample: a triangle mesh needs D == 3", __FILE__, __LINE__);
+    if (t != WL_F32 && t != WL_F64) return fail(WL_E_ARG, "wl_surface_sample: unknown dtype", __FILE__, __LINE__);
+    if (!p || !u) return fail(WL_E_ARG, "wl_surface_sample: null p or u", __FILE__, __LINE__);
+    if (!(std::isfinite(delta) && delta >= 0.0)) return fail(WL_E_ARG, "wl_surface_sample: delta must be finite and >= 0", __FILE__, __LINE__);
+    if (!std::isfinite(nu)) return fail(WL_E_ARG, "wl_surface_sample: nu must be finite", __FILE__, __LINE__);
+    if (mean_dev && !first && !(w > 0.0 && w <= 1.0)) return fail(WL_E_ARG, "wl_surface_sample: the mean's weight w must lie in (0, 1]", __FILE__, __LINE__);
+    PoseDev P;
+    WL_TRY(mesh_pose(m, pose, 0.0, P));
+    WL_TRY(mesh_upload(m));
+    const G gg = mkG(g);
+    const MeshDev M = m->view(true);
+    if (t == WL_F32)
+        return op_surface_sample<float>(gg, M, m->nt, P, (const float *)p, (const float *)u, delta, nu, rows_dev, geom_dev, mean_dev, w, first);
+    return op_surface_sample<double>(gg, M, m->nt, P, (const double *)p, (const double *)u, delta, nu, rows_dev, geom_dev, mean_dev, w, first);
+}
+int wl_surface_totals(const double *rows_dev, const double *geom_dev, int64_t nt, const double x0[3], double *out_dev) {
+    if (!rows_dev || !geom_dev || !x0 || !out_dev) return fail(WL_E_ARG, "wl_surface_totals: null rows, geometry, x0 or output", __FILE__, __LINE__);
+    if (nt <= 0) return fail(WL_E_ARG, "wl_surface_totals: nt must be positive", __FILE__, __LINE__);
+    if (!(std::isfinite(x0[0]) && std::isfinite(x0[1]) && std::isfinite(x0[2]))) return fail(WL_E_ARG, "wl_surface_totals: x0 must be finite", __FILE__, __LINE__);
+    int rc = 0;
+    Scratch &S = global_scratch(&rc);
+    WL_TRY(rc);
+    return op_surface_totals(rows_dev, geom_dev, nt, x0, S.partials, out_dev);
 }
 int wl_tracer_advance(wl_dtype t, const wl_grid *g, const void *u, double *x_dev, int64_t m, double dt, int perdir_mask) {
     WL_TRY(check_grid(g));

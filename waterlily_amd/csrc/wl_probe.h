@@ -75,6 +75,14 @@ __device__ __forceinline__ double probe_interp(const G &g, const T *__restrict__
     return s;
 }
 
+// does this rank own the entry sampled at p (the point AFTER the stagger shift)?  See "z-slabs" above.
+template <int D>
+__device__ __forceinline__ bool probe_owned(const ProbeZ &z, const double (&p)[D]) {
+    if (D != 3 || !z.dist) return true;
+    const double fz = floor(p[D - 1]) - 1.0;                      // the entry's floor plane, 0-based global
+    return (fz == fz) ? ((fz >= z.glo || z.first) && (fz <= z.ghi || z.last)) : z.first;
+}
+
 // out[q*ldo + c] = interp(x_q (+ 0.5 e_c), a_c), c < max(1, nc); nc = 0: scalar field
 template <class T, int D>
 __global__ void __launch_bounds__(256) k_interp(const G g, const ProbeZ z, const T *__restrict__ a, int nc,
@@ -89,12 +97,7 @@ __global__ void __launch_bounds__(256) k_interp(const G g, const ProbeZ z, const
         double p[D];
 #pragma unroll
         for (int d = 0; d < D; ++d) p[d] = (nc != 0 && d == c) ? x[d] + 0.5 : x[d];
-        bool mine = true;
-        if (D == 3 && z.dist) {
-            const double fz = floor(p[D - 1]) - 1.0;              // the entry's floor plane, 0-based global
-            mine = (fz == fz) ? ((fz >= z.glo || z.first) && (fz <= z.ghi || z.last)) : z.first;
-        }
-        out[q * ldo + c] = mine ? probe_interp<T, D>(g, a + (long)c * g.sc, p) : 0.0;
+        out[q * ldo + c] = probe_owned<D>(z, p) ? probe_interp<T, D>(g, a + (long)c * g.sc, p) : 0.0;
     }
 }
 
