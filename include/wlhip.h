@@ -416,6 +416,50 @@ int wl_surface_sample(wl_dtype t, const wl_grid *g, const void *p, const void *u
                       double delta, double nu, double *rows_dev, double *geom_dev, double *mean_dev, double w, int first);
 int wl_surface_totals(const double *rows_dev, const double *geom_dev, int64_t nt, const double x0[3], double *out_dev);
 
+/* ------------------------------------------------------------------ isosurface of a scalar field (Isosurface, waterlily_amd/iso.py)
+ * The triangles of the level set a == c of a cell-centred scalar field on a wl_grid (D == 3, either T, pitched or dense), by
+ * marching tetrahedra on the Kuhn split of every cube (csrc/wl_iso.h).  Every value is converted to double before its first use.
+ *   cube       : the 8 elements J .. J + (1,1,1), J 0-based, its low corner.  Output coordinates are x = J - 0.5 with GLOBAL z:
+ *                the frame of loc(0, I), in which MeshBody vertices and SurfaceLoads centroids live.
+ *   box        : cubes with lo_d <= J_d < hi_d are visited.  lo == hi == NULL: lo = 1, hi_d = n_d - 2 (nzg - 2 along z), all
+ *                corners in inside(a), which is all wl_metric fills.  Any 0 <= lo_d <= hi_d <= n_d - 1 is allowed for a caller
+ *                whose ghost cells are current.
+ *   tetrahedra : 6 per cube, one per permutation (p0,p1,p2) of the axes in lexicographic order 012, 021, 102, 120, 201, 210, with
+ *                local corners v0 = J, v1 = v0 + e_p0, v2 = v1 + e_p1, v3 = J + (1,1,1).  Every edge runs from a corner to a
+ *                componentwise >= corner, and the split is translation invariant: neighbouring cubes agree on face diagonals.
+ *   inside     : corner q is inside iff a_q < c.  A cube with a NaN corner emits nothing.
+ *   vertex     : on the edge between local corners p < q (always the lower linear index first): t = (c - a_p) / (a_q - a_p),
+ *                x_d = P_d + t where Q_d != P_d, else P_d.  Both cubes sharing an edge produce the same bits, so the surface is
+ *                watertight by bit equality.
+ *   triangles  : with I the inside and O the outside local corners, both ascending:  |I| = 1: (I0-O0, I0-O1, I0-O2);
+ *                |I| = 3: (I0-O0, I1-O0, I2-O0);  |I| = 2: the quad q0 = I0-O0, q1 = I0-O1, q2 = I1-O1, q3 = I1-O0 as (q0,q1,q2) then
+ *                (q0,q2,q3).  The last two vertices of a triangle are swapped where needed so that its normal points to the a >= c
+ *                side; whether to swap depends on (tet, inside mask) alone and is decided with every crossing at its edge's
+ *                midpoint: the sign of n . (mean(O corners) - mean(I corners)).  A triangle with repeated vertices (some a_q == c)
+ *                is emitted as it falls out.
+ *   order      : cubes in ascending linear index (x fastest), then tet 0..5, then the order above; at most 12 per cube.  The order
+ *                is a function of the field alone.
+ *   colour     : b (or NULL): a second field on the same grid with the same T; vertex value b_p + t (b_q - b_p) in double.
+ * wl_iso_table (host only) returns the (tet, mask) rule -- bit v of mask: local corner v inside: out[0] = the number of triangles,
+ * then 3 entries per triangle, each 4*p + q for the edge between local corners p < q; unused entries are -1.
+ * wl_isosurface: tri_dev cap*9 doubles, vertex-major (triangle, vertex, xyz); val_dev cap*3 doubles, required iff b is given;
+ * count_dev[0] = the number of triangles the surface has, count_dev[1] = min(that, cap) = the number written.  Triangles with
+ * global number >= cap are not written and nothing beyond cap is touched; cap == 0 with tri_dev == NULL is a pure count.
+ * Refused with WL_E_ARG before the device is touched: NULL g, a or count_dev; D != 3; a bad box; c NaN or infinite; cap < 0;
+ * cap > 0 without tri_dev; b without val_dev or val_dev without b; only one of lo and hi.
+ * Asynchronous on the library's stream: a count pass (one wavefront per x-row of cubes), an exclusive scan over the
+ * (hi1 - lo1)(hi2 - lo2) rows, an emit pass that leaves rows without triangles before reading the field.  Row counts and
+ * offsets live in scratch the library owns, which grows only when a call has more rows than any before it: steady calls
+ * allocate nothing (wl_prof_allocs).  No atomics: the same field gives the same bits.
+ * z-slabs: a rank visits the cubes whose low-corner plane it owns, the box clipped in global z (rank P-1 visits no cube on the
+ * top ghost plane: it would need a plane above; on a ring rank 0 also takes the bottom ghost plane, which nobody owns).  The
+ * kernel reads the first halo plane above the owned ones, so THE CALLER MUST HAVE EXCHANGED a AND b TO DEPTH 1
+ * (wl_halo_exchange): the output of wl_metric is not exchanged.  The ranks' outputs concatenated in rank order are the
+ * undecomposed output bit for bit; nothing is communicated.  WaterLily v1.3 has no such function to override. */
+int wl_iso_table(int tet, int mask, int32_t out[7]);
+int wl_isosurface(wl_dtype t, const wl_grid *g, const void *a, const void *b, double c, const int32_t lo[3], const int32_t hi[3],
+                  double *tri_dev, double *val_dev, int64_t cap, int64_t *count_dev);
+
 /* ------------------------------------------------------------------ snapshots (VTK write / restart,ext/WaterLilyWriteVTKExt.jl:57-66,
  * ext/WaterLilyReadVTKExt.jl:28-45).  The reference copies whole fields to the host (`a.flow.u |> Array`) and permutes the vector
  * components to the front there (components_first, :79).  Here the field's LOCAL planes klo..khi are packed on the device into

@@ -220,6 +220,8 @@ def lib() -> C.CDLL:
         "wl_tracer_advance": (i, [i, gp, vp, vp, i64, d, i]),
         "wl_surface_sample": (i, [i, gp, vp, vp, vp, C.POINTER(MeshPose), d, d, vp, vp, vp, d, i]),
         "wl_surface_totals": (i, [vp, vp, i64, dp, vp]),
+        "wl_iso_table": (i, [i, i, C.POINTER(C.c_int32)]),
+        "wl_isosurface": (i, [i, gp, vp, vp, d, C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, vp, i64, vp]),
         "wl_snapshot_pack": (i, [i, gp, vp, i, i, i, i, vp]),
         "wl_snapshot_unpack": (i, [i, gp, vp, i, i, i, i, vp]),
         "wl_set_option": (i, [i, i]),

@@ -17,6 +17,7 @@
 #include "wl_probe.h"
 #include "wl_integrals.h"
 #include "wl_surface.h"
+#include "wl_iso.h"
 
 namespace wl {
 
@@ -1645,6 +1646,39 @@ int wl_surface_totals(const double *rows_dev, const double *geom_dev, int64_t nt
     Scratch &S = global_scratch(&rc);
     WL_TRY(rc);
     return op_surface_totals(rows_dev, geom_dev, nt, x0, S.partials, out_dev);
+}
+int wl_iso_table(int tet, int mask, int32_t out[7]) {
+    if (tet < 0 || tet > 5 || mask < 0 || mask > 15) return fail(WL_E_ARG, "wl_iso_table: tet must lie in 0..5 and mask in 0..15", __FILE__, __LINE__);
+    if (!out) return fail(WL_E_ARG, "wl_iso_table: null output", __FILE__, __LINE__);
+    const uint32_t w = ISO_TRI[tet][mask];
+    const int nt = (int)(w >> 24);
+    out[0] = nt;
+    for (int k = 0; k < 6; ++k) out[1 + k] = k < 3 * nt ? (int32_t)((w >> (4 * k)) & 15u) : -1;
+    return 0;
+}
+int wl_isosurface(wl_dtype t, const wl_grid *g, const void *a, const void *b, double c, const int32_t lo[3], const int32_t hi[3],
+                  double *tri_dev, double *val_dev, int64_t cap, int64_t *count_dev) {
+    if (!g || !a || !count_dev) return fail(WL_E_ARG, "wl_isosurface: null grid, field or count", __FILE__, __LINE__);
+    WL_TRY(check_grid(g));
+    if (g->D != 3) return fail(WL_E_ARG, "wl_isosurface: an isosurface needs D == 3", __FILE__, __LINE__);
+    if (t != WL_F32 && t != WL_F64) return fail(WL_E_ARG, "wl_isosurface: unknown dtype", __FILE__, __LINE__);
+    if (!std::isfinite(c)) return fail(WL_E_ARG, "wl_isosurface: the level c must be finite", __FILE__, __LINE__);
+    if (cap < 0) return fail(WL_E_ARG, "wl_isosurface: negative capacity", __FILE__, __LINE__);
+    if (cap > 0 && !tri_dev) return fail(WL_E_ARG, "wl_isosurface: null triangle buffer with cap > 0", __FILE__, __LINE__);
+    if ((b != nullptr) != (val_dev != nullptr))
+        return fail(WL_E_ARG, "wl_isosurface: the colour field b and val_dev must be given together", __FILE__, __LINE__);
+    if ((lo != nullptr) != (hi != nullptr)) return fail(WL_E_ARG, "wl_isosurface: only one of lo and hi given", __FILE__, __LINE__);
+    const G gg = mkG(g);
+    int l[3], h[3];
+    for (int d = 0; d < 3; ++d) {
+        const int n = d == 2 ? gg.nzg : gg.n[d];
+        l[d] = lo ? lo[d] : 1;
+        h[d] = hi ? hi[d] : n - 2;
+        if (!(0 <= l[d] && l[d] <= h[d] && h[d] <= n - 1))
+            return fail(WL_E_ARG, "wl_isosurface: bad box (0 <= lo <= hi <= n - 1 in every direction)", __FILE__, __LINE__);
+    }
+    if (t == WL_F32) return op_isosurface<float>(gg, (const float *)a, (const float *)b, c, l, h, tri_dev, val_dev, cap, count_dev);
+    return op_isosurface<double>(gg, (const double *)a, (const double *)b, c, l, h, tri_dev, val_dev, cap, count_dev);
 }
 int wl_tracer_advance(wl_dtype t, const wl_grid *g, const void *u, double *x_dev, int64_t m, double dt, int perdir_mask) {
     WL_TRY(check_grid(g));
