@@ -26,26 +26,38 @@ typedef struct wlo_grid {
 
 #define WLO_MAXLEV 16
 
-/* middle eigenvalue of a symmetric 3x3 matrix (closed form): lambda2 = eigvals(Hermitian(S^2+Omega^2))[2] */
-static double wlo_sym3_mid_eig(double a00, double a01, double a02, double a11, double a12, double a22) {
-    const double p1 = a01 * a01 + a02 * a02 + a12 * a12;
-    const double q = (a00 + a11 + a22) / 3.0;
-    if (p1 == 0.0) {
-        double x = a00, y = a11, z = a22, t;
-        if (x > y) { t = x; x = y; y = t; }
-        if (y > z) { t = y; y = z; z = t; }
-        if (x > y) { t = x; x = y; y = t; }
-        return y;
+/* One Jacobi rotation of a symmetric 3x3 matrix in the (p,q) plane (Golub & Van Loan 8.5): zeroes apq; dp, dq are the two
+ * diagonal entries, arp and arq the entries that couple the third index to p and to q.  A theta whose square overflows
+ * gives t = 0: apq is then far below an ulp of dq - dp and is dropped. */
+#define WLO_JACOBI_ROT(dp, dq, apq, arp, arq)                                              \
+    if ((apq) != 0.0) {                                                                    \
+        const double th_ = ((dq) - (dp)) / (2.0 * (apq));                                  \
+        const double t_ = copysign(1.0, th_) / (fabs(th_) + sqrt(th_ * th_ + 1.0));        \
+        const double c_ = 1.0 / sqrt(t_ * t_ + 1.0), s_ = t_ * c_, x_ = (arp);             \
+        (dp) -= t_ * (apq);                                                                \
+        (dq) += t_ * (apq);                                                                \
+        (apq) = 0.0;                                                                       \
+        (arp) = c_ * x_ - s_ * (arq);                                                      \
+        (arq) = s_ * x_ + c_ * (arq);                                                      \
     }
-    const double b00 = a00 - q, b11 = a11 - q, b22 = a22 - q;
-    const double p2 = b00 * b00 + b11 * b11 + b22 * b22 + 2.0 * p1;
-    const double p = sqrt(p2 / 6.0);
-    const double c00 = b00 / p, c11 = b11 / p, c22 = b22 / p, c01 = a01 / p, c02 = a02 / p, c12 = a12 / p;
-    double r = 0.5 * (c00 * (c11 * c22 - c12 * c12) - c01 * (c01 * c22 - c12 * c02) + c02 * (c01 * c12 - c11 * c02));
-    r = r < -1.0 ? -1.0 : (r > 1.0 ? 1.0 : r);
-    const double phi = acos(r) / 3.0;
-    const double e1 = q + 2.0 * p * cos(phi), e3 = q + 2.0 * p * cos(phi + 2.0943951023931953);
-    return 3.0 * q - e1 - e3;
+/* middle eigenvalue of a symmetric 3x3 matrix: lambda2 = eigvals(Hermitian(S^2+Omega^2))[2].  Cyclic Jacobi sweeps (the
+ * same sequence as sym3_mid_eig of wl_api.hip): every rotation is orthogonal to rounding, so the error stays a few
+ * eps * ||A|| however close two eigenvalues lie -- the trigonometric closed form takes acos(r) at r = +-1 there and
+ * keeps only half the digits.  A diagonal matrix takes no rotation: its sorted diagonal comes back exactly.  Cyclic Jacobi
+ * converges quadratically: after 4 to 5 sweeps a 3x3 matrix is diagonal to working precision and further rotations change
+ * nothing.  The loop leaves early only when every off-diagonal entry is exactly zero (a diagonal input, or underflow), so a
+ * generic matrix runs all 8 sweeps. */
+static double wlo_sym3_mid_eig(double a00, double a01, double a02, double a11, double a12, double a22) {
+    for (int sweep = 0; sweep < 8 && (a01 != 0.0 || a02 != 0.0 || a12 != 0.0); ++sweep) {
+        WLO_JACOBI_ROT(a00, a11, a01, a02, a12)
+        WLO_JACOBI_ROT(a00, a22, a02, a01, a12)
+        WLO_JACOBI_ROT(a11, a22, a12, a01, a02)
+    }
+    double x = a00, y = a11, z = a22, t;
+    if (x > y) { t = x; x = y; y = t; }
+    if (y > z) { t = y; y = z; z = t; }
+    if (x > y) { t = x; x = y; y = t; }
+    return y;
 }
 
 #define T float

@@ -540,26 +540,38 @@ static int bdim_full(const G &g, T *u, const T *u0, T *f, const T *V, const T *m
     WL_TRY((op_bdim1<T, D>(g, f, u0, V, dt)));
     return op_bdim2<T, D, 0>(g, u, f, V, mu0, mu1);
 }
-// middle eigenvalue of a symmetric 3x3 matrix (closed form, Smith 1961) -- lambda2 = eigvals(Hermitian(S^2+O^2))[2]
+// One Jacobi rotation of a symmetric 3x3 matrix in the (p,q) plane (Golub & Van Loan 8.5): zeroes apq; dp, dq are the two
+// diagonal entries, arp and arq the entries that couple the third index to p and to q.  A theta whose square overflows gives
+// t = 0: apq is then far below an ulp of dq - dp and is dropped.
+__host__ __device__ inline void jacobi_rot(double &dp, double &dq, double &apq, double &arp, double &arq) {
+    if (apq == 0.0) return;
+    const double th = (dq - dp) / (2.0 * apq);
+    const double t = copysign(1.0, th) / (fabs(th) + sqrt(th * th + 1.0));
+    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c, x = arp;
+    dp -= t * apq;
+    dq += t * apq;
+    apq = 0.0;
+    arp = c * x - s * arq;
+    arq = s * x + c * arq;
+}
+// middle eigenvalue of a symmetric 3x3 matrix -- lambda2 = eigvals(Hermitian(S^2+O^2))[2].  Cyclic Jacobi sweeps: every
+// rotation is orthogonal to rounding, so the error stays a few eps * ||A|| however close two eigenvalues lie (solid
+// rotation, plane shear, any axisymmetric region); the trigonometric closed form takes acos(r) at r = +-1 there and keeps
+// only half the digits.  A diagonal matrix takes no rotation: its sorted diagonal comes back exactly.  Cyclic Jacobi
+// converges quadratically: after 4 to 5 sweeps a 3x3 matrix is diagonal to working precision and further rotations change
+// nothing.  The loop leaves early only when every off-diagonal entry is exactly zero (a diagonal input, or underflow), so a
+// generic matrix runs all 8 sweeps: 24 rotations of 2 sqrt and 2 divisions each, per cell, in a post-processing kernel.
 __host__ __device__ inline double sym3_mid_eig(double a00, double a01, double a02, double a11, double a12, double a22) {
-    const double p1 = a01 * a01 + a02 * a02 + a12 * a12;
-    const double q = (a00 + a11 + a22) / 3.0;
-    if (p1 == 0.0) {   // diagonal
-        double x = a00, y = a11, z = a22, t;
-        if (x > y) { t = x; x = y; y = t; }
-        if (y > z) { t = y; y = z; z = t; }
-        if (x > y) { t = x; x = y; y = t; }
-        return y;
+    for (int sweep = 0; sweep < 8 && (a01 != 0.0 || a02 != 0.0 || a12 != 0.0); ++sweep) {
+        jacobi_rot(a00, a11, a01, a02, a12);
+        jacobi_rot(a00, a22, a02, a01, a12);
+        jacobi_rot(a11, a22, a12, a01, a02);
     }
-    const double b00 = a00 - q, b11 = a11 - q, b22 = a22 - q;
-    const double p2 = b00 * b00 + b11 * b11 + b22 * b22 + 2.0 * p1;
-    const double p = sqrt(p2 / 6.0);
-    const double c00 = b00 / p, c11 = b11 / p, c22 = b22 / p, c01 = a01 / p, c02 = a02 / p, c12 = a12 / p;
-    double r = 0.5 * (c00 * (c11 * c22 - c12 * c12) - c01 * (c01 * c22 - c12 * c02) + c02 * (c01 * c12 - c11 * c02));
-    r = r < -1.0 ? -1.0 : (r > 1.0 ? 1.0 : r);
-    const double phi = acos(r) / 3.0;
-    const double e1 = q + 2.0 * p * cos(phi), e3 = q + 2.0 * p * cos(phi + 2.0943951023931953);
-    return 3.0 * q - e1 - e3;
+    double x = a00, y = a11, z = a22, t;
+    if (x > y) { t = x; x = y; y = t; }
+    if (y > z) { t = y; y = z; z = t; }
+    if (x > y) { t = x; x = y; y = t; }
+    return y;
 }
 template <class T, int D>
 static int op_metric(const G &g, int kind, T *out, const T *u, int ipar, const double *par, const double *par2) {
