@@ -85,6 +85,42 @@ def test_no_gpu_fails_loudly():
         sim.Flow((16, 16), (1.0, 0.0))
 
 
+def test_create_without_gpu_fails_clean():
+    """wl_flow_create and wl_mg_create with valid descriptors but no device: the first allocation fails, the call returns an
+    error, hands out no handle and drops what it had made; a second call behaves the same (nothing half-built is left)."""
+    import torch
+    if torch.cuda.is_available():
+        pytest.skip("GPU present")
+    L = _lib.lib()
+
+    def grid(n):
+        g = _lib.Grid()
+        g.D = 3
+        g.n[:] = [n, n, n]
+        g.s[:] = [1, n, n * n]
+        g.sc = n ** 3
+        return g
+
+    host = (C.c_float * (3 * 18 ** 3))()   # never reached: the descriptors only have to pass validation
+    fd = _lib.FlowDesc()
+    fd.g = grid(18)
+    for k in ("u", "u0", "f", "p", "sigma", "V", "mu0", "mu1"):
+        setattr(fd, k, C.addressof(host))
+    fd.nu = 0.01
+    levels = (_lib.LevelDesc * 3)()
+    for lv, n in zip(levels, (18, 10, 6)):
+        lv.g = grid(n)
+        for k in ("L", "D", "iD", "x", "eps", "r", "z"):
+            setattr(lv, k, C.addressof(host))
+    for _ in range(2):   # (a HIP error number, below 10000: the descriptors passed validation and the device refused)
+        h = C.c_void_p()
+        rc = L.wl_flow_create(C.byref(h), _lib.WL_F32, C.byref(fd))
+        assert 0 < rc < 10000 and h.value is None and b"wlhip error" in L.wl_last_error(), (rc, L.wl_last_error())
+        h = C.c_void_p()
+        rc = L.wl_mg_create(C.byref(h), _lib.WL_F32, 3, levels, 0)
+        assert 0 < rc < 10000 and h.value is None and b"wlhip error" in L.wl_last_error(), (rc, L.wl_last_error())
+
+
 def test_abi_v6_entry_points_validate_without_gpu():
     """ABI v6 additions reject bad calls before touching the device: pitched copies whose row is wider than a pitch, snapshot
     staging with a bad tuple / plane range, the loopback communicator's rank, option queries of retired keys."""

@@ -1,6 +1,7 @@
 // wl_api.hip -- C ABI (include/wlhip.h) + host orchestration: Vcycle!, solver!, project!, mom_step!.
 #include <cstdarg>
 #include <cstring>
+#include <memory>
 
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -67,14 +68,8 @@ struct RcclComm : Comm {
 // synchronises the stream and stages through pinned host memory: correct, not fast.
 struct HostComm : Comm {
     wl_host_sendrecv_fn sr; wl_host_allreduce_fn ar; wl_host_allgather_fn ag; void *user;
-    char *pin = nullptr; size_t cap = 0;
-    ~HostComm() override { if (pin) (void)hipHostFree(pin); }
-    int need(size_t b) {
-        if (b <= cap) return 0;
-        if (pin) (void)hipHostFree(pin);
-        cap = b * 2;
-        return (int)wl_host_alloc((void **)&pin, cap, hipHostMallocDefault);
-    }
+    Buf<char, PinnedMem<hipHostMallocDefault>> pin;   // staging, grown to twice what the call needs
+    int need(size_t b) { return pin.reserve(b, b * 2); }
     int do_allreduce(double *dev, int n, int op) override {
         double v[8];
         WL_HIP(hipMemcpyAsync(v, dev, sizeof(double) * n, hipMemcpyDeviceToHost, ctx().stream));
@@ -86,7 +81,7 @@ struct HostComm : Comm {
     }
     int do_sendrecv(const void *slo, void *rlo, const void *shi, void *rhi, size_t bytes, int plo, int phi) override {
         WL_TRY(need(4 * bytes));
-        char *hs_lo = pin, *hr_lo = pin + bytes, *hs_hi = pin + 2 * bytes, *hr_hi = pin + 3 * bytes;
+        char *hs_lo = pin.get(), *hr_lo = hs_lo + bytes, *hs_hi = hs_lo + 2 * bytes, *hr_hi = hs_lo + 3 * bytes;
         if (slo) WL_HIP(hipMemcpyAsync(hs_lo, slo, bytes, hipMemcpyDeviceToHost, ctx().stream));
         if (shi) WL_HIP(hipMemcpyAsync(hs_hi, shi, bytes, hipMemcpyDeviceToHost, ctx().stream));
         WL_HIP(hipStreamSynchronize(ctx().stream));
@@ -100,10 +95,10 @@ struct HostComm : Comm {
     int do_allgather(void *buf, size_t bytes) override {
         const size_t tot = bytes * (size_t)size;
         WL_TRY(need(tot));
-        WL_HIP(hipMemcpyAsync(pin + (size_t)rank * bytes, (char *)buf + (size_t)rank * bytes, bytes, hipMemcpyDeviceToHost, ctx().stream));
+        WL_HIP(hipMemcpyAsync(pin.get() + (size_t)rank * bytes, (char *)buf + (size_t)rank * bytes, bytes, hipMemcpyDeviceToHost, ctx().stream));
         WL_HIP(hipStreamSynchronize(ctx().stream));
-        if (ag(user, pin, (int64_t)bytes)) return fail(WL_E_STATE, "host allgather callback failed", __FILE__, __LINE__);
-        WL_HIP(hipMemcpyAsync(buf, pin, tot, hipMemcpyHostToDevice, ctx().stream));
+        if (ag(user, pin.get(), (int64_t)bytes)) return fail(WL_E_STATE, "host allgather callback failed", __FILE__, __LINE__);
+        WL_HIP(hipMemcpyAsync(buf, pin.get(), tot, hipMemcpyHostToDevice, ctx().stream));
         WL_HIP(hipStreamSynchronize(ctx().stream));
         return 0;
     }
@@ -193,35 +188,30 @@ int check_grid(const wl_grid *g) {
 
 // ------------------------------------------------------------------------------------------ handles
 struct Scratch {
-    double *partials = nullptr;  // 4 * WL_MAXB doubles
-    State *st = nullptr;         // device
-    State *hst = nullptr;        // pinned host mirror
+    Buf<double, DevMem> partials;                           // 4 * WL_MAXB doubles
+    Buf<State, DevMem> st;                                  // device
+    Buf<State, PinnedMem<hipHostMallocDefault>> hst;        // pinned host mirror
     int init() {
-        WL_HIP(wl_dev_alloc((void **)&partials, sizeof(double) * 4 * WL_MAXB));
-        WL_HIP(wl_dev_alloc((void **)&st, sizeof(State)));
-        WL_HIP(hipMemset(st, 0, sizeof(State)));
-        WL_HIP(wl_host_alloc((void **)&hst, sizeof(State), hipHostMallocDefault));
-        memset(hst, 0, sizeof(State));
+        WL_TRY(partials.reserve(4 * WL_MAXB));
+        WL_TRY(st.reserve(1));
+        WL_HIP(hipMemset(st.get(), 0, sizeof(State)));
+        WL_TRY(hst.reserve(1));
+        memset(hst.get(), 0, sizeof(State));
         return 0;
-    }
-    void release() {
-        if (partials) (void)hipFree(partials);
-        if (st) (void)hipFree(st);
-        if (hst) (void)hipHostFree(hst);
-        partials = nullptr; st = nullptr; hst = nullptr;
     }
     // bring the device scalars to the host (synchronises the stream)
     int fetch() {
-        WL_HIP(hipMemcpyAsync(hst, st, sizeof(State), hipMemcpyDeviceToHost, ctx().stream));
+        WL_HIP(hipMemcpyAsync(hst.get(), st.get(), sizeof(State), hipMemcpyDeviceToHost, ctx().stream));
         WL_HIP(hipStreamSynchronize(ctx().stream));
-        if (ctx().mbox && *ctx().mbox->err_host)
+        if (ctx().mbox && *ctx().mbox->err_host.get())
             return fail(WL_E_STATE, "mailbox all-reduce: gave up waiting for a peer rank (is every rank still running?)", __FILE__, __LINE__);
         return 0;
     }
 };
 
 Scratch &global_scratch(int *rc) {
-    static Scratch s;
+    // never destroyed: a static's destructor would free device memory at exit, when the HIP runtime may already be gone
+    static Scratch &s = *new Scratch();
     static bool ok = false;
     *rc = 0;
     if (!ok) { *rc = s.init(); ok = (*rc == 0); }
@@ -239,25 +229,18 @@ struct wl_mg {
     int permask;
     std::vector<wl_level_desc> lev;
     Scratch sc;
-    std::vector<void *> rowc;            // per level: row constants of L and iD (k_lrow), RC_N values per (j,k) row; D==3 only
-    unsigned char *dirty = nullptr;      // level-0 row flags of wl_mg_update_changed
+    std::vector<Buf<unsigned char, DevMem>> rowc;   // per level: row constants of L and iD (k_lrow), RC_N values per (j,k) row; D==3 only
+    Buf<unsigned char, DevMem> dirty;    // level-0 row flags of wl_mg_update_changed
     bool log_on = false;                 // wl_mg_log: record {n, Linf, L2} per solver iteration
     std::vector<double> log;
     int alloc_rowc() {
         const size_t es = t == WL_F32 ? 4 : 8;
-        rowc.assign(nlev, nullptr);
+        rowc.resize(nlev);
         for (int l = 0; l < nlev; ++l) {
             const wl_grid &g = lev[l].g;
-            if (g.D != 3) continue;
-            WL_HIP(wl_dev_alloc(&rowc[l], (size_t)g.n[1] * (size_t)g.n[2] * RC_N * es));
+            if (g.D == 3) WL_TRY(rowc[l].reserve((size_t)g.n[1] * (size_t)g.n[2] * RC_N * es));
         }
         return 0;
-    }
-    void free_scratch() {
-        for (void *p : rowc) if (p) (void)hipFree(p);
-        rowc.clear();
-        if (dirty) (void)hipFree(dirty);
-        dirty = nullptr;
     }
 };
 struct wl_flow {
@@ -265,19 +248,18 @@ struct wl_flow {
     wl_flow_desc d;
     Scratch sc;
     unsigned char *rowfree = nullptr;   // body-free row flags (wl_flow_update); nullptr until built
-    unsigned char *rowbuf = nullptr;
-    unsigned char *segbuf = nullptr;    // the same per 64-cell segment of a row (3-D; wl_flow_update's scan only)
+    Buf<unsigned char, DevMem> rowbuf;  // what rowfree points at once built
+    Buf<unsigned char, DevMem> segbuf;  // the same per 64-cell segment of a row (3-D; wl_flow_update's scan only)
     bool seg_valid = false;
-    const unsigned char *segfree() const { return (seg_valid && opt(WL_OPT_BDIM_ROWFLAGS)) ? segbuf : nullptr; }
-    int *busy = nullptr;                // compact list of the busy interior rows (j + n1*k), device
+    const unsigned char *segfree() const { return (seg_valid && opt(WL_OPT_BDIM_ROWFLAGS)) ? segbuf.get() : nullptr; }
+    Buf<int, DevMem> busy;              // compact list of the busy interior rows (j + n1*k), device
     int nbusy = 0;
     int nbusy_lo = 0, nbusy_hi = 0;      // how many of them lie in the first / last owned interior plane (the list is sorted by plane)
-    size_t busy_cap = 0;
     // native measure! (wl_measure.h): per-row band counts / offsets, rows touched by this and by the previous measure!
-    int *rowcount = nullptr;
-    long *rowoff = nullptr;
-    unsigned char *touched = nullptr, *prev = nullptr;
-    unsigned char *changed = nullptr;   // rows whose coefficient arrays the last native measure! rewrote (touched now or before)
+    Buf<int, DevMem> rowcount;
+    Buf<long, DevMem> rowoff;
+    Buf<unsigned char, DevMem> touched, prev;
+    Buf<unsigned char, DevMem> changed; // rows whose coefficient arrays the last native measure! rewrote (touched now or before)
     bool changed_valid = false;
     bool changed_pending = false;       // `changed` holds rows no update!(pois) has consumed yet: the next measure! ORs into it
     bool prev_valid = false;            // `prev` describes the arrays' current content (else: rewrite every row)
@@ -289,7 +271,7 @@ template <class T> static LevelT<T> lvl(const wl_mg *m, int l) {
     LevelT<T> o;
     o.g = mkG(&d.g);
     o.L = (T *)d.L; o.D = (T *)d.D; o.iD = (T *)d.iD; o.x = (T *)d.x; o.eps = (T *)d.eps; o.r = (T *)d.r; o.z = (T *)d.z;
-    o.rowc = (opt(WL_OPT_ROW_CONST_L) && l < (int)m->rowc.size()) ? (const T *)m->rowc[l] : nullptr;
+    o.rowc = (opt(WL_OPT_ROW_CONST_L) && l < (int)m->rowc.size()) ? (const T *)m->rowc[l].get() : nullptr;
     return o;
 }
 
@@ -301,7 +283,7 @@ template <class T, int D> static int mg_update(wl_mg *m, const unsigned char *di
         LevelT<T> p = lvl<T>(m, 0);
         WL_TRY((op_set_diag<T, D>(p.g, p.D, p.iD, p.L, dirty)));
         WL_TRY((halo_exchange<T>(p.g, p.iD, 1, 1)));   // z-slab: the fused smoother evaluates r*iD in the halo planes
-        if (D == 3 && m->rowc[0]) WL_TRY((op_lrow<T>(p.g, p.L, p.iD, (T *)m->rowc[0], dirty)));
+        if (D == 3 && m->rowc[0].get()) WL_TRY((op_lrow<T>(p.g, p.L, p.iD, (T *)m->rowc[0].get(), dirty)));
     }
     for (int l = 1; l < m->nlev; ++l) {
         LevelT<T> a = lvl<T>(m, l), b = lvl<T>(m, l - 1);
@@ -309,7 +291,7 @@ template <class T, int D> static int mg_update(wl_mg *m, const unsigned char *di
         WL_TRY((coarse_L_finish<T, D>(a.g, a.L, b.g, m->permask)));
         WL_TRY((op_set_diag<T, D>(a.g, a.D, a.iD, a.L)));
         WL_TRY((halo_exchange<T>(a.g, a.iD, 1, 1)));
-        if (D == 3 && m->rowc[l]) WL_TRY((op_lrow<T>(a.g, a.L, a.iD, (T *)m->rowc[l])));
+        if (D == 3 && m->rowc[l].get()) WL_TRY((op_lrow<T>(a.g, a.L, a.iD, (T *)m->rowc[l].get())));
     }
     return 0;
 }
@@ -355,10 +337,10 @@ template <class T, int D> static int mg_vcycle(wl_mg *m, int l, int *pcg_np = nu
     if (!tail) {
         int pre = -1;
         if (l + 2 < m->nlev) WL_TRY((mg_vcycle<T, D>(m, l + 1, pcg_np ? &pre : nullptr)));
-        WL_TRY((op_pcg<T, D>(coarse, 6, m->permask, m->sc.partials, m->sc.st, false, pre)));
+        WL_TRY((op_pcg<T, D>(coarse, 6, m->permask, m->sc.partials.get(), m->sc.st.get(), false, pre)));
     }
     if (pcg_np) *pcg_np = -1;
-    if (fused) return op_prolong_increment_fused<T, D>(fine, fine.eps, coarse.g, coarse.x, m->sc.partials, pcg_np);
+    if (fused) return op_prolong_increment_fused<T, D>(fine, fine.eps, coarse.g, coarse.x, m->sc.partials.get(), pcg_np);
     WL_TRY((op_prolongate<T, D>(fine.g, fine.eps, coarse.g, coarse.x)));
     return op_increment<T, D>(fine, m->permask);
 }
@@ -371,30 +353,30 @@ template <class T, int D> static int mg_Linf(wl_mg *m, int l) {
     LevelT<T> p = lvl<T>(m, l);
     const T *r = p.r;
     return op_reduce<T, D>(p.g, WL_K_DOT, RED_MAX, 0.0, [=] __device__(long I) { const double v = (double)r[I]; return v < 0 ? -v : v; },
-                           m->sc.partials, m->sc.st, 1, true);   // the whole array, ghost cells included
+                           m->sc.partials.get(), m->sc.st.get(), 1, true);   // the whole array, ghost cells included
 }
 // one row of the reference's solver log: `@log ", $n, $(L∞(p)), $r₂\n"` (Poisson.jl:164,167; MultiLevelPoisson.jl:90,94)
 template <class T, int D> static int mg_log_row(wl_mg *m, int n, bool have_r2) {
-    if (!have_r2) WL_TRY((op_L2<T, D>(lvl<T>(m, 0), m->sc.partials, m->sc.st, false)));
+    if (!have_r2) WL_TRY((op_L2<T, D>(lvl<T>(m, 0), m->sc.partials.get(), m->sc.st.get(), false)));
     WL_TRY((mg_Linf<T, D>(m, 0)));
     WL_TRY(m->sc.fetch());
-    m->log.push_back((double)n); m->log.push_back(m->sc.hst->out[1]); m->log.push_back(m->sc.hst->r2);
+    m->log.push_back((double)n); m->log.push_back(m->sc.hst.get()->out[1]); m->log.push_back(m->sc.hst.get()->r2);
     return 0;
 }
 template <class T, int D> static int mg_solve(wl_mg *m, double tol, int itmx, int *n_iter, const T *divu = nullptr, const G *gu = nullptr,
                                               bool halo_begun = false) {
     LevelT<T> p = lvl<T>(m, 0);
-    WL_TRY((op_residual<T, D>(p, m->permask, m->sc.partials, m->sc.st, divu, gu, halo_begun)));
+    WL_TRY((op_residual<T, D>(p, m->permask, m->sc.partials.get(), m->sc.st.get(), divu, gu, halo_begun)));
     int n = 0;
     if (m->log_on) WL_TRY((mg_log_row<T, D>(m, 0, false)));
     while (n < itmx) {
         int pre = -1;
         if (m->nlev > 1) WL_TRY((mg_vcycle<T, D>(m, 0, &pre)));
-        WL_TRY((op_pcg<T, D>(p, 6, m->permask, m->sc.partials, m->sc.st, true, pre, true)));   // (level 1: z ≡ flow.σ)
-        WL_TRY((op_L2<T, D>(p, m->sc.partials, m->sc.st, true)));
+        WL_TRY((op_pcg<T, D>(p, 6, m->permask, m->sc.partials.get(), m->sc.st.get(), true, pre, true)));   // (level 1: z ≡ flow.σ)
+        WL_TRY((op_L2<T, D>(p, m->sc.partials.get(), m->sc.st.get(), true)));
         WL_TRY(m->sc.fetch());
         ++n;
-        const double r2 = m->sc.hst->r2;
+        const double r2 = m->sc.hst.get()->r2;
         if (m->log_on) WL_TRY((mg_log_row<T, D>(m, n, true)));
         if (r2 < tol) break;
     }
@@ -470,7 +452,7 @@ static int flow_mom_step(wl_flow *a, wl_mg *b, double dt, const double *U, const
     // and BDIM! #2 is a pass of its own, in place.
     bool turns = false;
     if constexpr (D == 3)
-        turns = opt(WL_OPT_BDIM_IN_CONVDIFF) && opt(WL_OPT_BDIM_ROWFLAGS) && a->rowfree && a->busy && d.perdir_mask == 0 && !d.exitBC && conv_diff_tiled<D>(g, 0);
+        turns = opt(WL_OPT_BDIM_IN_CONVDIFF) && opt(WL_OPT_BDIM_ROWFLAGS) && a->rowfree && a->busy.get() && d.perdir_mask == 0 && !d.exitBC && conv_diff_tiled<D>(g, 0);
     T *const up = turns ? u0 : u;   // where the predictor's velocity u' lives
     const CdFin<T> fin1{up, a->rowfree, xbc.on, (T)U[0]}, fin2{u, a->rowfree, xbc.on, (T)U[0]};
     (void)fin1; (void)fin2;
@@ -479,7 +461,7 @@ static int flow_mom_step(wl_flow *a, wl_mg *b, double dt, const double *U, const
     if (turns) {
         if constexpr (D == 3) {
             WL_TRY((op_conv_diff<T, D, true, false, 1>(g, f, u, d.nu, 0, u, V, dt, gp, gp != nullptr, nullptr, false, &fin1)));
-            WL_TRY((op_bdim2_busy<T, 1>(g, up, up, f, V, mu0, mu1, a->busy, a->nbusy, a->nbusy_lo, a->nbusy_hi, xbc, a->segfree())));   // + exchange of f
+            WL_TRY((op_bdim2_busy<T, 1>(g, up, up, f, V, mu0, mu1, a->busy.get(), a->nbusy, a->nbusy_lo, a->nbusy_hi, xbc, a->segfree())));   // + exchange of f
             xd = xbc.on != 0;
         }
     } else {
@@ -488,10 +470,10 @@ static int flow_mom_step(wl_flow *a, wl_mg *b, double dt, const double *U, const
         // z⋅ϵ in the projection that follows (periodic runs only: elsewhere ϵ's ghosts are zero) and by maximum(a.σ) in CFL --
         // which sees the corrector's values, so a non-periodic run skips the predictor's.
         if (d.perdir_mask != 0) WL_TRY((op_sigma_ghosts<T, D>(g, (T *)d.sigma, u, d.nu, d.perdir_mask)));
-        WL_TRY((op_bdim2<T, D, 1>(g, u, f, V, mu0, mu1, a->rowfree, a->busy, a->nbusy, true, &xbc, &xd, a->segfree())));   // + exchange of f (overlapped)
+        WL_TRY((op_bdim2<T, D, 1>(g, u, f, V, mu0, mu1, a->rowfree, a->busy.get(), a->nbusy, true, &xbc, &xd, a->segfree())));   // + exchange of f (overlapped)
     }
     WL_TRY((op_bc_vec<T, D>(g, up, U, d.exitBC, d.perdir_mask, xd)));
-    if (d.exitBC) WL_TRY((op_exit_bc<T, D>(g, up, u0, U, dt, a->sc.partials, a->sc.st)));
+    if (d.exitBC) WL_TRY((op_exit_bc<T, D>(g, up, u0, U, dt, a->sc.partials.get(), a->sc.st.get())));
     // (the predictor's closing `x ./= dt` and the corrector's opening `x .*= 0.5dt` are ONE pass over x: nothing in between reads p)
     const ScaleOp corr_head = project_scale<T>(dt, 0.5);
     const bool chain = opt(WL_OPT_SCALE_CHAIN) != 0;
@@ -503,37 +485,37 @@ static int flow_mom_step(wl_flow *a, wl_mg *b, double dt, const double *U, const
         if constexpr (D == 3) {
             WL_TRY((op_conv_diff<T, D, true, false, 2>(g, f, up, d.nu, 0, u, V, dt, gc, gc != nullptr, nullptr, true, &fin2)));
             WL_TRY((op_sigma_ghosts<T, D>(g, (T *)d.sigma, up, d.nu, 0)));
-            WL_TRY((op_bdim2_busy<T, 2>(g, u, up, f, V, mu0, mu1, a->busy, a->nbusy, a->nbusy_lo, a->nbusy_hi, xbc, a->segfree())));
+            WL_TRY((op_bdim2_busy<T, 2>(g, u, up, f, V, mu0, mu1, a->busy.get(), a->nbusy, a->nbusy_lo, a->nbusy_hi, xbc, a->segfree())));
             xd = xbc.on != 0;
         }
     } else {
         WL_TRY((op_conv_diff<T, D, true>(g, f, u, d.nu, d.perdir_mask, u0, V, dt, gc, gc != nullptr, nullptr, true)));
         WL_TRY((op_sigma_ghosts<T, D>(g, (T *)d.sigma, u, d.nu, d.perdir_mask)));
-        WL_TRY((op_bdim2<T, D, 2>(g, u, f, V, mu0, mu1, a->rowfree, a->busy, a->nbusy, true, &xbc, &xd, a->segfree())));
+        WL_TRY((op_bdim2<T, D, 2>(g, u, f, V, mu0, mu1, a->rowfree, a->busy.get(), a->nbusy, true, &xbc, &xd, a->segfree())));
     }
     WL_TRY((op_bc_vec<T, D>(g, u, U, d.exitBC, d.perdir_mask, xd)));
     WL_TRY((flow_project<T, D>(a, b, dt, 0.5, &n2[1], true, chain, nullptr, &xbc, &xd)));
     WL_TRY((op_bc_vec<T, D>(g, u, U, d.exitBC, d.perdir_mask, xd)));
     // push!(a.dt, CFL(a)) (:168); the end-of-step 2-plane exchange of u is issued inside (overlapped with the kernel)
-    WL_TRY((op_cfl<T, D>(g, (T *)d.sigma, u, d.nu, a->sc.partials, a->sc.st, true)));
+    WL_TRY((op_cfl<T, D>(g, (T *)d.sigma, u, d.nu, a->sc.partials.get(), a->sc.st.get(), true)));
     WL_TRY(a->sc.fetch());
-    *dt_next = a->sc.hst->out[0];
+    *dt_next = a->sc.hst.get()->out[0];
     return 0;
 }
 
 template <class T, int D> static int red_L2(const G &g, const T *a, Scratch &S) {
     return op_reduce<T, D>(g, WL_K_DOT, RED_SUM, 0.0, [=] __device__(long I) { const double v = (double)a[I]; return v * v; },
-                           S.partials, S.st, 0);
+                           S.partials.get(), S.st.get(), 0);
 }
 template <class T, int D> static int red_dot(const G &g, const T *a, const T *b, Scratch &S) {
     return op_reduce<T, D>(g, WL_K_DOT, RED_SUM, 0.0, [=] __device__(long I) { return (double)a[I] * (double)b[I]; },
-                           S.partials, S.st, 0, true);
+                           S.partials.get(), S.st.get(), 0, true);
 }
 template <class T, int D> static int red_sum(const G &g, const T *a, Scratch &S) {
-    return op_reduce<T, D>(g, WL_K_DOT, RED_SUM, 0.0, [=] __device__(long I) { return (double)a[I]; }, S.partials, S.st, 0, true);
+    return op_reduce<T, D>(g, WL_K_DOT, RED_SUM, 0.0, [=] __device__(long I) { return (double)a[I]; }, S.partials.get(), S.st.get(), 0, true);
 }
 template <class T, int D> static int red_max(const G &g, const T *a, Scratch &S) {
-    return op_reduce<T, D>(g, WL_K_DOT, RED_MAX, -1e300, [=] __device__(long I) { return (double)a[I]; }, S.partials, S.st, 0, true);
+    return op_reduce<T, D>(g, WL_K_DOT, RED_MAX, -1e300, [=] __device__(long I) { return (double)a[I]; }, S.partials.get(), S.st.get(), 0, true);
 }
 template <class T, int D>
 static int bdim_full(const G &g, T *u, const T *u0, T *f, const T *V, const T *mu0, const T *mu1, double dt) {
@@ -695,23 +677,19 @@ __global__ __launch_bounds__(256) void k_pforce(const T *p, const int64_t *idx, 
 }
 // compact the busy INTERIOR rows of a->rowbuf on the host (n1*n2 bytes; this runs once per measure!, not per step)
 static int flow_compact_busy(wl_flow *a, const G &g, int D) {
-    a->rowfree = a->rowbuf;
+    a->rowfree = a->rowbuf.get();
     const size_t nrows = (size_t)g.n[1] * (size_t)(D > 2 ? g.n[2] : 1);
     std::vector<unsigned char> fl(nrows);
-    WL_HIP(hipMemcpyAsync(fl.data(), a->rowbuf, nrows, hipMemcpyDeviceToHost, ctx().stream));
+    WL_HIP(hipMemcpyAsync(fl.data(), a->rowbuf.get(), nrows, hipMemcpyDeviceToHost, ctx().stream));
     WL_HIP(hipStreamSynchronize(ctx().stream));
     const Range R = r_inside(g);
     std::vector<int> list;
     for (int k = R.lo[2]; k <= R.hi[2]; ++k)
         for (int j = 1; j <= g.n[1] - 2; ++j)
             if (!fl[(size_t)j + (size_t)g.n[1] * k]) list.push_back(j + g.n[1] * k);
-    if (list.size() > a->busy_cap) {
-        if (a->busy) (void)hipFree(a->busy);
-        a->busy_cap = list.size() * 2 + 64;
-        WL_HIP(wl_dev_alloc((void **)&a->busy, a->busy_cap * sizeof(int)));
-    }
-    if (!a->busy) { a->busy_cap = 64; WL_HIP(wl_dev_alloc((void **)&a->busy, a->busy_cap * sizeof(int))); }
-    if (!list.empty()) WL_HIP(hipMemcpyAsync(a->busy, list.data(), list.size() * sizeof(int), hipMemcpyHostToDevice, ctx().stream));
+    const size_t nl = list.size();   // never left without a list: 64 entries for an empty one, 2n + 64 when n do not fit
+    WL_TRY(a->busy.reserve(nl ? nl : 1, nl ? nl * 2 + 64 : 64));
+    if (!list.empty()) WL_HIP(hipMemcpyAsync(a->busy.get(), list.data(), list.size() * sizeof(int), hipMemcpyHostToDevice, ctx().stream));
     WL_HIP(hipStreamSynchronize(ctx().stream));
     a->nbusy = (int)list.size();
     a->nbusy_lo = a->nbusy_hi = 0;
@@ -723,8 +701,8 @@ static int flow_compact_busy(wl_flow *a, const G &g, int D) {
 }
 template <class T, int D> static int flow_update(wl_flow *a) {
     const G g = mkG(&a->d.g);
-    WL_TRY((op_rowflags<T, D>(g, (const T *)a->d.V, (const T *)a->d.mu0, (const T *)a->d.mu1, a->rowbuf, a->d.perdir_mask, D == 3 ? a->segbuf : nullptr)));
-    a->seg_valid = (D == 3 && a->segbuf != nullptr);
+    WL_TRY((op_rowflags<T, D>(g, (const T *)a->d.V, (const T *)a->d.mu0, (const T *)a->d.mu1, a->rowbuf.get(), a->d.perdir_mask, D == 3 ? a->segbuf.get() : nullptr)));
+    a->seg_valid = (D == 3 && a->segbuf.get() != nullptr);
     a->prev_valid = false;   // the arrays were written by someone else: the next native measure! rewrites every row
     return flow_compact_busy(a, g, D);
 }
@@ -743,12 +721,12 @@ static BodyDev body_dev(const wl_body_desc *bodies) {
     return o;
 }
 static int measure_alloc(wl_flow *a, size_t nrows) {
-    if (a->rowcount) return 0;
-    WL_HIP(wl_dev_alloc((void **)&a->rowcount, nrows * sizeof(int)));
-    WL_HIP(wl_dev_alloc((void **)&a->rowoff, (nrows + 1) * sizeof(long)));
-    WL_HIP(wl_dev_alloc((void **)&a->touched, nrows));
-    WL_HIP(wl_dev_alloc((void **)&a->prev, nrows));
-    WL_HIP(wl_dev_alloc((void **)&a->changed, nrows));
+    // one by one: after a failure part-way the next call allocates what is missing instead of trusting the first
+    WL_TRY(a->rowcount.reserve(nrows));
+    WL_TRY(a->rowoff.reserve(nrows + 1));
+    WL_TRY(a->touched.reserve(nrows));
+    WL_TRY(a->prev.reserve(nrows));
+    WL_TRY(a->changed.reserve(nrows));
     return 0;
 }
 // The two halves of a native measure! with the body's own kernels passed in: `rows(g, nrows, d2)` launches the sigma / band
@@ -763,11 +741,11 @@ template <class T, int D, class Rows> static int measure_rows_with(wl_flow *a, d
         Prof p(WL_K_MISC, g.cells());
         rows(g, nrows, d2);
         WL_HIP(hipGetLastError());
-        hipLaunchKernelGGL(k_scan_rows, dim3(1), dim3(1024), 0, ctx().stream, (const int *)a->rowcount, a->rowoff, (long)nrows);
+        hipLaunchKernelGGL(k_scan_rows, dim3(1), dim3(1024), 0, ctx().stream, (const int *)a->rowcount.get(), a->rowoff.get(), (long)nrows);
         WL_HIP(hipGetLastError());
     }
     long tot = 0;
-    WL_HIP(hipMemcpyAsync(&tot, a->rowoff + nrows, sizeof(long), hipMemcpyDeviceToHost, ctx().stream));
+    WL_HIP(hipMemcpyAsync(&tot, a->rowoff.get() + nrows, sizeof(long), hipMemcpyDeviceToHost, ctx().stream));
     WL_HIP(hipStreamSynchronize(ctx().stream));
     a->nband = tot;
     *nband = tot;
@@ -777,7 +755,7 @@ template <class T, int D> static int measure_rows(wl_flow *a, const wl_body_desc
     const BodyDev B = body_dev(body);
     return measure_rows_with<T, D>(a, eps, nband, [&](const G &g, size_t nrows, T d2) {
         hipLaunchKernelGGL((k_measure_rows<T, D>), dim3((unsigned)((nrows + 3) / 4)), dim3(256), 0, ctx().stream, g, B, (T *)a->d.sigma, d2,
-                           a->rowcount, a->touched);
+                           a->rowcount.get(), a->touched.get());
     });
 }
 template <class T, int D, class Fill> static int measure_fill_with(wl_flow *a, int64_t *cand, Fill fill) {
@@ -797,14 +775,14 @@ template <class T, int D, class Fill> static int measure_fill_with(wl_flow *a, i
     WL_TRY((halo_exchange<T>(g, (T *)a->d.V, D, 2)));
     a->seg_valid = false;   // (the native measure! knows touched ROWS only: every segment of a busy row takes the general statement)
     hipLaunchKernelGGL((k_rowflags_touched<D>), dim3((unsigned)((nrows + 255) / 256)), dim3(256), 0, ctx().stream, g,
-                       (const unsigned char *)a->touched, a->rowbuf, a->d.perdir_mask);
+                       (const unsigned char *)a->touched.get(), a->rowbuf.get(), a->d.perdir_mask);
     WL_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_rows_changed, dim3((unsigned)((nrows + 255) / 256)), dim3(256), 0, ctx().stream, (const unsigned char *)a->touched,
-                       (const unsigned char *)a->prev, !a->prev_valid, a->changed_valid && a->changed_pending, a->changed, (long)nrows);
+    hipLaunchKernelGGL(k_rows_changed, dim3((unsigned)((nrows + 255) / 256)), dim3(256), 0, ctx().stream, (const unsigned char *)a->touched.get(),
+                       (const unsigned char *)a->prev.get(), !a->prev_valid, a->changed_valid && a->changed_pending, a->changed.get(), (long)nrows);
     WL_HIP(hipGetLastError());
     a->changed_valid = true;
     a->changed_pending = true;
-    WL_HIP(hipMemcpyAsync(a->prev, a->touched, nrows, hipMemcpyDeviceToDevice, ctx().stream));
+    WL_HIP(hipMemcpyAsync(a->prev.get(), a->touched.get(), nrows, hipMemcpyDeviceToDevice, ctx().stream));
     WL_TRY(flow_compact_busy(a, g, D));
     a->prev_valid = true;
     return 0;
@@ -814,38 +792,31 @@ template <class T, int D> static int measure_fill(wl_flow *a, const wl_body_desc
     const T d2 = (T)((2 + eps) * (2 + eps));
     return measure_fill_with<T, D>(a, cand, [&](const G &g, size_t nrows, int64_t *cd) {
         hipLaunchKernelGGL((k_measure_fill<T, D>), dim3((unsigned)((nrows + 3) / 4)), dim3(256), 0, ctx().stream, g, B, (const T *)a->d.sigma, d2,
-                           (2 + eps) * (2 + eps), eps, (T *)a->d.mu0, (T *)a->d.mu1, (T *)a->d.V, (const unsigned char *)a->touched,
-                           (const unsigned char *)a->prev, !a->prev_valid, (const long *)a->rowoff, (long *)cd);
+                           (2 + eps) * (2 + eps), eps, (T *)a->d.mu0, (T *)a->d.mu1, (T *)a->d.V, (const unsigned char *)a->touched.get(),
+                           (const unsigned char *)a->prev.get(), !a->prev_valid, (const long *)a->rowoff.get(), (long *)cd);
     });
 }
 // ---- triangle-mesh bodies (wl_mesh.h)
 static int mesh_upload(const wl_mesh *m) {
-    if (m->d_tri) return 0;
-    // the handle's pointers are set only once all four copies are on the device: a failure part-way frees what it made and
+    if (m->d_tri.get()) return 0;
+    // the handle's buffers are set only once all four copies are on the device: a failure part-way drops the locals and
     // leaves the handle as it was (not uploaded), so a later call starts again instead of launching with half the arrays
-    double *tri = nullptr;
-    int *start = nullptr, *list = nullptr;
-    signed char *sign = nullptr;
-    const size_t nlist = std::max<size_t>(m->bin_tri.size(), 1);
-    hipError_t e = wl_dev_alloc((void **)&tri, m->tri.size() * sizeof(double));
-    if (e == hipSuccess) e = wl_dev_alloc((void **)&start, m->bin_start.size() * sizeof(int));
-    if (e == hipSuccess) e = wl_dev_alloc((void **)&list, nlist * sizeof(int));
-    if (e == hipSuccess) e = wl_dev_alloc((void **)&sign, m->bin_sign.size());
-    if (e == hipSuccess) e = hipMemcpyAsync(tri, m->tri.data(), m->tri.size() * sizeof(double), hipMemcpyHostToDevice, ctx().stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(start, m->bin_start.data(), m->bin_start.size() * sizeof(int), hipMemcpyHostToDevice, ctx().stream);
+    Buf<double, DevMem> tri;
+    Buf<int, DevMem> start, list;
+    Buf<signed char, DevMem> sign;
+    WL_TRY(tri.reserve(m->tri.size()));
+    WL_TRY(start.reserve(m->bin_start.size()));
+    WL_TRY(list.reserve(std::max<size_t>(m->bin_tri.size(), 1)));
+    WL_TRY(sign.reserve(m->bin_sign.size()));
+    hipError_t e = hipMemcpyAsync(tri.get(), m->tri.data(), m->tri.size() * sizeof(double), hipMemcpyHostToDevice, ctx().stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(start.get(), m->bin_start.data(), m->bin_start.size() * sizeof(int), hipMemcpyHostToDevice, ctx().stream);
     if (e == hipSuccess && !m->bin_tri.empty())
-        e = hipMemcpyAsync(list, m->bin_tri.data(), m->bin_tri.size() * sizeof(int), hipMemcpyHostToDevice, ctx().stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(sign, m->bin_sign.data(), m->bin_sign.size(), hipMemcpyHostToDevice, ctx().stream);
+        e = hipMemcpyAsync(list.get(), m->bin_tri.data(), m->bin_tri.size() * sizeof(int), hipMemcpyHostToDevice, ctx().stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(sign.get(), m->bin_sign.data(), m->bin_sign.size(), hipMemcpyHostToDevice, ctx().stream);
     const hipError_t es = hipStreamSynchronize(ctx().stream);   // (also on failure: no copy may still be reading the host arrays)
     if (e == hipSuccess) e = es;
-    if (e != hipSuccess) {
-        if (tri) (void)hipFree(tri);
-        if (start) (void)hipFree(start);
-        if (list) (void)hipFree(list);
-        if (sign) (void)hipFree(sign);
-        return fail((int)e, "uploading the mesh bins", __FILE__, __LINE__);
-    }
-    m->d_start = start; m->d_list = list; m->d_sign = sign; m->d_tri = tri;
+    if (e != hipSuccess) return fail((int)e, "uploading the mesh bins", __FILE__, __LINE__);
+    m->d_start = std::move(start); m->d_list = std::move(list); m->d_sign = std::move(sign); m->d_tri = std::move(tri);
     return 0;
 }
 // the pose as the kernels take it; refuses a map that is not a similarity (A A^T = s^2 I) or whose exact zone R/s is too thin
@@ -881,7 +852,7 @@ template <class T> static int mesh_rows(wl_flow *a, const wl_mesh *m, const Pose
     const MeshDev M = m->view(true);
     return measure_rows_with<T, 3>(a, eps, nband, [&](const G &g, size_t nrows, T d2) {
         hipLaunchKernelGGL((k_mesh_rows<T>), dim3((unsigned)((nrows + 3) / 4)), dim3(256), 0, ctx().stream, g, M, P, (T *)a->d.sigma, d2,
-                           a->rowcount, a->touched);
+                           a->rowcount.get(), a->touched.get());
     });
 }
 template <class T> static int mesh_fill(wl_flow *a, const wl_mesh *m, const PoseDev &P, double eps, int64_t *cand) {
@@ -890,8 +861,8 @@ template <class T> static int mesh_fill(wl_flow *a, const wl_mesh *m, const Pose
     const T d2 = (T)((2 + eps) * (2 + eps));
     return measure_fill_with<T, 3>(a, cand, [&](const G &g, size_t nrows, int64_t *cd) {
         hipLaunchKernelGGL((k_mesh_fill<T>), dim3((unsigned)((nrows + 3) / 4)), dim3(256), 0, ctx().stream, g, M, P, (const T *)a->d.sigma, d2,
-                           (2 + eps) * (2 + eps), eps, (T *)a->d.mu0, (T *)a->d.mu1, (T *)a->d.V, (const unsigned char *)a->touched,
-                           (const unsigned char *)a->prev, !a->prev_valid, (const long *)a->rowoff, (long *)cd);
+                           (2 + eps) * (2 + eps), eps, (T *)a->d.mu0, (T *)a->d.mu1, (T *)a->d.V, (const unsigned char *)a->touched.get(),
+                           (const unsigned char *)a->prev.get(), !a->prev_valid, (const long *)a->rowoff.get(), (long *)cd);
     });
 }
 static int check_body(const wl_body_desc *b, int D) {
@@ -919,11 +890,11 @@ template <class KERNEL> static int band_reduce(const G &gg, Scratch &S, int64_t 
         launch(nb);
         WL_HIP(hipGetLastError());
     }
-    State *st = S.st;
-    WL_TRY((launch_finalize<3>(gg.dist, S.partials, nb, RED_SUM, 0.0, st->red, [=] __device__(const double *v) {
+    State *st = S.st.get();
+    WL_TRY((launch_finalize<3>(gg.dist, S.partials.get(), nb, RED_SUM, 0.0, st->red, [=] __device__(const double *v) {
         st->out[0] = v[0]; st->out[1] = v[1]; st->out[2] = v[2]; })));
     WL_TRY(S.fetch());
-    for (int c = 0; c < D; ++c) out[c] = S.hst->out[c];
+    for (int c = 0; c < D; ++c) out[c] = S.hst.get()->out[c];
     return 0;
 }
 // Snapshot staging (VTK write / restart): planes klo..khi of a field <-> a DENSE array-of-tuples buffer on the device,
@@ -1007,7 +978,6 @@ static void mailbox_release() {
     Mailbox *mb = ctx().mbox;
     if (!mb) return;
     if (mb->host) { (void)hipHostUnregister(mb->host); munmap(mb->host, mb->bytes); }
-    if (mb->err_host) (void)hipHostFree(mb->err_host);
     delete mb;
     ctx().mbox = nullptr;
 }
@@ -1035,13 +1005,12 @@ int wl_comm_mailbox(const char *shm_name, int create) {
     mb->host = (MboxSlot *)p;
     void *dp = nullptr;
     e = hipHostGetDevicePointer(&dp, p, 0);
-    if (e == hipSuccess) e = wl_host_alloc((void **)&mb->err_host, sizeof(int), hipHostMallocMapped);
-    if (e == hipSuccess) { *mb->err_host = 0; e = hipHostGetDevicePointer((void **)&mb->err_dev, mb->err_host, 0); }
-    if (e != hipSuccess) {
+    int rc = e == hipSuccess ? mb->err_host.reserve(1) : (int)e;
+    if (!rc) { *mb->err_host.get() = 0; rc = (int)hipHostGetDevicePointer((void **)&mb->err_dev, mb->err_host.get(), 0); }
+    if (rc) {
         (void)hipHostUnregister(p); munmap(p, bytes);
-        if (mb->err_host) (void)hipHostFree(mb->err_host);
         delete mb;
-        return fail((int)e, "wl_comm_mailbox: device mapping", __FILE__, __LINE__);
+        return fail(rc, "wl_comm_mailbox: device mapping", __FILE__, __LINE__);
     }
     mb->dev = (MboxSlot *)dp;
     if (ctx().wall_khz <= 0.0) {   // ticks per millisecond of wall_clock64() (constant-rate counter: 100 MHz on gfx9)
@@ -1093,10 +1062,10 @@ int wl_allreduce(double *vals, int n, int op) {
     int rc = 0;
     Scratch &S = global_scratch(&rc);
     WL_TRY(rc);
-    WL_HIP(hipMemcpyAsync(S.st->red, vals, sizeof(double) * n, hipMemcpyHostToDevice, ctx().stream));
+    WL_HIP(hipMemcpyAsync(S.st.get()->red, vals, sizeof(double) * n, hipMemcpyHostToDevice, ctx().stream));
     const double init = op == 0 ? 0.0 : -1e300;
     // (np = 1: the "partials" are the values themselves; st->out doubles as the staging so that input and output differ)
-    double *in = S.st->red, *out4 = S.st->out;
+    double *in = S.st.get()->red, *out4 = S.st.get()->out;
     int rc2 = 0;
     if (ctx().mbox) {
         WL_HIP(hipMemcpyAsync(out4, in, sizeof(double) * n, hipMemcpyDeviceToDevice, ctx().stream));
@@ -1106,11 +1075,11 @@ int wl_allreduce(double *vals, int n, int op) {
             case 3: rc2 = reduce_allreduce<3>(out4, 1, op, init, in); break;
             default: rc2 = reduce_allreduce<4>(out4, 1, op, init, in); break;
         }
-    } else rc2 = cm->allreduce(S.st->red, n, op);
+    } else rc2 = cm->allreduce(S.st.get()->red, n, op);
     WL_TRY(rc2);
-    WL_HIP(hipMemcpyAsync(vals, S.st->red, sizeof(double) * n, hipMemcpyDeviceToHost, ctx().stream));
+    WL_HIP(hipMemcpyAsync(vals, S.st.get()->red, sizeof(double) * n, hipMemcpyDeviceToHost, ctx().stream));
     WL_HIP(hipStreamSynchronize(ctx().stream));
-    if (ctx().mbox && *ctx().mbox->err_host)
+    if (ctx().mbox && *ctx().mbox->err_host.get())
         return fail(WL_E_STATE, "mailbox all-reduce: gave up waiting for a peer rank (is every rank still running?)", __FILE__, __LINE__);
     return 0;
 }
@@ -1171,7 +1140,7 @@ int wl_bc_per(wl_dtype t, const wl_grid *g, void *a, int perdir_mask) {
 }
 int wl_exit_bc(wl_dtype t, const wl_grid *g, void *u, const void *u0, const double U[3], double dt) {
     WL_GS();
-    WL_DISPATCH(t, g->D, (op_exit_bc<T, DD>(gg, (T *)u, (const T *)u0, U, dt, S.partials, S.st)));
+    WL_DISPATCH(t, g->D, (op_exit_bc<T, DD>(gg, (T *)u, (const T *)u0, U, dt, S.partials.get(), S.st.get())));
 }
 
 #define WL_RED(CALL)                 \
@@ -1179,7 +1148,7 @@ int wl_exit_bc(wl_dtype t, const wl_grid *g, void *u, const void *u0, const doub
         int r1__ = [&]() -> int { WL_DISPATCH(t, g->D, CALL); }(); \
         if (r1__) return r1__;       \
         WL_TRY(S.fetch());           \
-        *out = S.hst->out[0];        \
+        *out = S.hst.get()->out[0];        \
         return 0;                    \
     } while (0)
 
@@ -1224,7 +1193,7 @@ int wl_div(wl_dtype t, const wl_grid *g, void *z, const void *u) {
 }
 int wl_cfl(wl_dtype t, const wl_grid *g, void *sigma, const void *u, double nu, double *out) {
     WL_GS();
-    WL_RED((op_cfl<T, DD>(gg, (T *)sigma, (const T *)u, nu, S.partials, S.st)));
+    WL_RED((op_cfl<T, DD>(gg, (T *)sigma, (const T *)u, nu, S.partials.get(), S.st.get())));
 }
 int wl_set_diag(wl_dtype t, const wl_grid *g, void *Dg, void *iD, const void *L) {
     WL_GS();
@@ -1265,23 +1234,18 @@ int wl_mg_create(wl_mg **out, wl_dtype t, int nlevels, const wl_level_desc *leve
                     return fail(WL_E_ARG, "wl_mg_create: level extents must be 1+N/2 of the finer level", __FILE__, __LINE__);
             }
     }
-    wl_mg *m = new wl_mg();
+    std::unique_ptr<wl_mg> m(new wl_mg());   // (an error return drops the handle and with it every buffer made so far)
     m->t = t; m->D = levels[0].g.D; m->nlev = nlevels; m->permask = perdir_mask;
     m->lev.assign(levels, levels + nlevels);
-    int rc = m->sc.init();
-    if (rc) { delete m; return rc; }
-    rc = m->alloc_rowc();
-    if (rc) { m->free_scratch(); m->sc.release(); delete m; return rc; }
-    rc = wl_mg_update(m);
-    if (rc) { m->free_scratch(); m->sc.release(); delete m; return rc; }
-    *out = m;
+    WL_TRY(m->sc.init());
+    WL_TRY(m->alloc_rowc());
+    WL_TRY(wl_mg_update(m.get()));
+    *out = m.release();
     return 0;
 }
 int wl_mg_destroy(wl_mg *m) {
     if (!m) return 0;
     (void)hipStreamSynchronize(ctx().stream);
-    m->sc.release();
-    m->free_scratch();
     delete m;
     return 0;
 }
@@ -1295,17 +1259,17 @@ int wl_mg_update_changed(wl_mg *m, wl_flow *a) {
     const wl_grid &gm = m->lev[0].g, &gf = a->d.g;
     // a periodic z across slabs (ring): the ghost plane's source row lives on another rank -> full update
     const bool zper = (m->permask >> 2) & 1, yper = (m->permask >> 1) & 1;
-    const bool usable = a->changed_valid && a->changed && m->D == 3 && gf.D == 3 && gm.n[0] == gf.n[0] && gm.n[1] == gf.n[1] &&
-                        gm.n[2] == gf.n[2] && m->lev[0].L == a->d.mu0 && !m->rowc.empty() && m->rowc[0] && !(zper && gm.nzg > 0);
+    const bool usable = a->changed_valid && a->changed.get() && m->D == 3 && gf.D == 3 && gm.n[0] == gf.n[0] && gm.n[1] == gf.n[1] &&
+                        gm.n[2] == gf.n[2] && m->lev[0].L == a->d.mu0 && !m->rowc.empty() && m->rowc[0].get() && !(zper && gm.nzg > 0);
     a->changed_pending = false;   // consumed (by the partial or by the full update below)
     if (!usable) return wl_mg_update(m);
     const long nrows = (long)gm.n[1] * gm.n[2];
-    if (!m->dirty) WL_HIP(wl_dev_alloc((void **)&m->dirty, (size_t)nrows));
+    WL_TRY(m->dirty.reserve((size_t)nrows));
     // D, iD and the row constants of row (j,k) read L of the rows (j,k), (j+1,k), (j,k+1)
-    hipLaunchKernelGGL(k_rows_dirty, dim3((unsigned)((nrows + 255) / 256)), dim3(256), 0, ctx().stream, (const unsigned char *)a->changed,
-                       m->dirty, gm.n[1], gm.n[2], (int)yper, (int)zper);
+    hipLaunchKernelGGL(k_rows_dirty, dim3((unsigned)((nrows + 255) / 256)), dim3(256), 0, ctx().stream, (const unsigned char *)a->changed.get(),
+                       m->dirty.get(), gm.n[1], gm.n[2], (int)yper, (int)zper);
     WL_HIP(hipGetLastError());
-    const unsigned char *dirty = m->dirty;
+    const unsigned char *dirty = m->dirty.get();
     WL_MG_DISPATCH((mg_update<T, DD>(m, dirty)));
 }
 int wl_mg_mult(wl_mg *m, int level, void *x) {
@@ -1314,7 +1278,7 @@ int wl_mg_mult(wl_mg *m, int level, void *x) {
 }
 int wl_mg_residual(wl_mg *m, int level) {
     WL_LEVEL_OK();
-    WL_MG_DISPATCH((op_residual<T, DD>(lvl<T>(m, level), m->permask, m->sc.partials, m->sc.st)));
+    WL_MG_DISPATCH((op_residual<T, DD>(lvl<T>(m, level), m->permask, m->sc.partials.get(), m->sc.st.get())));
 }
 int wl_mg_increment(wl_mg *m, int level) {
     WL_LEVEL_OK();
@@ -1326,11 +1290,11 @@ int wl_mg_jacobi(wl_mg *m, int level, int it) {
 }
 int wl_mg_pcg(wl_mg *m, int level, int it, int *n_updates) {
     WL_LEVEL_OK();
-    int rc = [&]() -> int { WL_MG_DISPATCH((op_pcg<T, DD>(lvl<T>(m, level), it, m->permask, m->sc.partials, m->sc.st, false, -1, level == 0))); }();
+    int rc = [&]() -> int { WL_MG_DISPATCH((op_pcg<T, DD>(lvl<T>(m, level), it, m->permask, m->sc.partials.get(), m->sc.st.get(), false, -1, level == 0))); }();
     if (rc) return rc;
     if (n_updates) {
         WL_TRY(m->sc.fetch());
-        *n_updates = m->sc.hst->nupd;
+        *n_updates = m->sc.hst.get()->nupd;
     }
     return 0;
 }
@@ -1340,10 +1304,10 @@ int wl_mg_uniform_rows(wl_mg *m, int level, long long *n_uniform, long long *n_r
     const wl_grid &g = m->lev[level].g;
     *n_uniform = 0;
     *n_rows = (long long)(g.n[1] - 2) * (g.D == 3 ? (g.own_hi > 0 ? g.own_hi - g.own_lo + 1 : g.n[2] - 2) : 1);
-    if (g.D != 3 || level >= (int)m->rowc.size() || !m->rowc[level]) return 0;
+    if (g.D != 3 || level >= (int)m->rowc.size() || !m->rowc[level].get()) return 0;
     const size_t es = m->t == WL_F32 ? 4 : 8, cnt = (size_t)g.n[1] * g.n[2] * RC_N;
     std::vector<char> h(cnt * es);
-    WL_HIP(hipMemcpyAsync(h.data(), m->rowc[level], cnt * es, hipMemcpyDeviceToHost, ctx().stream));
+    WL_HIP(hipMemcpyAsync(h.data(), m->rowc[level].get(), cnt * es, hipMemcpyDeviceToHost, ctx().stream));
     WL_HIP(hipStreamSynchronize(ctx().stream));
     for (size_t r = 0; r < cnt; r += RC_N) {
         const double c = m->t == WL_F32 ? (double)reinterpret_cast<const float *>(h.data())[r] : reinterpret_cast<const double *>(h.data())[r];
@@ -1353,10 +1317,10 @@ int wl_mg_uniform_rows(wl_mg *m, int level, long long *n_uniform, long long *n_r
 }
 int wl_mg_L2(wl_mg *m, int level, double *out) {
     WL_LEVEL_OK();
-    int rc = [&]() -> int { WL_MG_DISPATCH((op_L2<T, DD>(lvl<T>(m, level), m->sc.partials, m->sc.st))); }();
+    int rc = [&]() -> int { WL_MG_DISPATCH((op_L2<T, DD>(lvl<T>(m, level), m->sc.partials.get(), m->sc.st.get()))); }();
     if (rc) return rc;
     WL_TRY(m->sc.fetch());
-    *out = m->sc.hst->r2;
+    *out = m->sc.hst.get()->r2;
     return 0;
 }
 int wl_mg_Linf(wl_mg *m, int level, double *out) {
@@ -1365,7 +1329,7 @@ int wl_mg_Linf(wl_mg *m, int level, double *out) {
     int rc = [&]() -> int { WL_MG_DISPATCH((mg_Linf<T, DD>(m, level))); }();
     if (rc) return rc;
     WL_TRY(m->sc.fetch());
-    *out = m->sc.hst->out[1];
+    *out = m->sc.hst.get()->out[1];
     return 0;
 }
 int wl_mg_log(wl_mg *m, int on) {
@@ -1399,34 +1363,21 @@ int wl_flow_create(wl_flow **out, wl_dtype t, const wl_flow_desc *d) {
     WL_TRY(check_grid(&d->g));
     if (!d->u || !d->u0 || !d->f || !d->p || !d->sigma || !d->V || !d->mu0 || !d->mu1)
         return fail(WL_E_ARG, "wl_flow_create: null field", __FILE__, __LINE__);
-    wl_flow *a = new wl_flow();
+    std::unique_ptr<wl_flow> a(new wl_flow());   // (an error return drops the handle and with it every buffer made so far)
     a->t = t; a->d = *d;
-    int rc = a->sc.init();
-    if (rc) { delete a; return rc; }
+    WL_TRY(a->sc.init());
     const size_t nrows = (size_t)d->g.n[1] * (size_t)(d->g.D > 2 ? d->g.n[2] : 1);
-    if (wl_dev_alloc((void **)&a->rowbuf, nrows) != hipSuccess) { a->sc.release(); delete a; return fail(WL_E_STATE, "wl_dev_alloc(row flags)", __FILE__, __LINE__); }
+    WL_TRY(a->rowbuf.reserve(nrows));
     if (d->g.D > 2) {
         const size_t ntx = (size_t)(d->g.n[0] - 2 + 63) / 64;
-        if (wl_dev_alloc((void **)&a->segbuf, nrows * (ntx ? ntx : 1)) != hipSuccess) {
-            (void)hipFree(a->rowbuf); a->sc.release(); delete a;
-            return fail(WL_E_STATE, "wl_dev_alloc(segment flags)", __FILE__, __LINE__);
-        }
+        WL_TRY(a->segbuf.reserve(nrows * (ntx ? ntx : 1)));
     }
-    *out = a;
+    *out = a.release();
     return 0;
 }
 int wl_flow_destroy(wl_flow *a) {
     if (!a) return 0;
     (void)hipStreamSynchronize(ctx().stream);
-    a->sc.release();
-    if (a->rowbuf) (void)hipFree(a->rowbuf);
-    if (a->segbuf) (void)hipFree(a->segbuf);
-    if (a->busy) (void)hipFree(a->busy);
-    if (a->rowcount) (void)hipFree(a->rowcount);
-    if (a->rowoff) (void)hipFree(a->rowoff);
-    if (a->touched) (void)hipFree(a->touched);
-    if (a->prev) (void)hipFree(a->prev);
-    if (a->changed) (void)hipFree(a->changed);
     delete a;
     return 0;
 }
@@ -1467,18 +1418,15 @@ int wl_mesh_create(wl_mesh **out, const double *vert_host, int64_t nv, const int
     if (nt > (int64_t)0x3fffffff || nv > (int64_t)0x7fffffff) return fail(WL_E_ARG, "wl_mesh_create: mesh too large", __FILE__, __LINE__);
     if (!(exact_radius > 3.0) || !std::isfinite(exact_radius))
         return fail(WL_E_ARG, "wl_mesh_create: exact_radius too small (needs 2 + eps + 1 with eps > 0)", __FILE__, __LINE__);
-    wl_mesh *m = new wl_mesh;
+    std::unique_ptr<wl_mesh> m(new wl_mesh);
     const char *err = mesh_build(*m, vert_host, nv, tri_host, nt, exact_radius);
-    if (err) { delete m; return fail(WL_E_ARG, err, __FILE__, __LINE__); }
-    *out = m;
+    if (err) return fail(WL_E_ARG, err, __FILE__, __LINE__);
+    *out = m.release();
     return 0;
 }
 int wl_mesh_destroy(wl_mesh *m) {
     if (!m) return 0;
-    if (m->d_tri) {
-        (void)hipStreamSynchronize(ctx().stream);
-        (void)hipFree(m->d_tri); (void)hipFree(m->d_start); (void)hipFree(m->d_list); (void)hipFree(m->d_sign);
-    }
+    if (m->d_tri.get()) (void)hipStreamSynchronize(ctx().stream);
     delete m;
     return 0;
 }
@@ -1566,8 +1514,8 @@ int wl_vforce(wl_dtype t, const wl_grid *g, const void *u, const int64_t *idx, c
               double out[3]) {
     WL_GS();
     return band_reduce(gg, S, nband, g->D, out, [&](int nb) {
-        if (t == WL_F32) hipLaunchKernelGGL(k_vforce<float>, dim3(nb), dim3(256), 0, ctx().stream, gg, (const float *)u, idx, nds, nband, (float)nu, S.partials);
-        else hipLaunchKernelGGL(k_vforce<double>, dim3(nb), dim3(256), 0, ctx().stream, gg, (const double *)u, idx, nds, nband, nu, S.partials);
+        if (t == WL_F32) hipLaunchKernelGGL(k_vforce<float>, dim3(nb), dim3(256), 0, ctx().stream, gg, (const float *)u, idx, nds, nband, (float)nu, S.partials.get());
+        else hipLaunchKernelGGL(k_vforce<double>, dim3(nb), dim3(256), 0, ctx().stream, gg, (const double *)u, idx, nds, nband, nu, S.partials.get());
     });
 }
 int wl_pmoment(wl_dtype t, const wl_grid *g, const void *p, const int64_t *idx, const double *nds, int64_t nband,
@@ -1575,8 +1523,8 @@ int wl_pmoment(wl_dtype t, const wl_grid *g, const void *p, const int64_t *idx, 
     WL_GS();
     const double a = x0[0], b = x0[1], c = g->D > 2 ? x0[2] : 0.0;
     return band_reduce(gg, S, nband, g->D, out, [&](int nb) {
-        if (t == WL_F32) hipLaunchKernelGGL(k_pmoment<float>, dim3(nb), dim3(256), 0, ctx().stream, gg, (const float *)p, idx, nds, nband, a, b, c, S.partials);
-        else hipLaunchKernelGGL(k_pmoment<double>, dim3(nb), dim3(256), 0, ctx().stream, gg, (const double *)p, idx, nds, nband, a, b, c, S.partials);
+        if (t == WL_F32) hipLaunchKernelGGL(k_pmoment<float>, dim3(nb), dim3(256), 0, ctx().stream, gg, (const float *)p, idx, nds, nband, a, b, c, S.partials.get());
+        else hipLaunchKernelGGL(k_pmoment<double>, dim3(nb), dim3(256), 0, ctx().stream, gg, (const double *)p, idx, nds, nband, a, b, c, S.partials.get());
     });
 }
 int wl_metric(wl_dtype t, const wl_grid *g, int kind, void *out, const void *u, int ipar, const double par[3],
@@ -1590,7 +1538,7 @@ int wl_flow_integrals(wl_dtype t, const wl_grid *g, const void *u, const double 
     if (!g || !u || !U || !row_dev) return fail(WL_E_ARG, "wl_flow_integrals: null grid, u, U or row", __FILE__, __LINE__);
     if (g->D != 2 && g->D != 3) return fail(WL_E_ARG, "wl_flow_integrals: D must be 2 or 3", __FILE__, __LINE__);
     WL_GS();
-    WL_DISPATCH(t, g->D, (op_integrals<T, DD>(gg, (const T *)u, U, S.partials, row_dev)));
+    WL_DISPATCH(t, g->D, (op_integrals<T, DD>(gg, (const T *)u, U, S.partials.get(), row_dev)));
 }
 int wl_meanflow_update(wl_dtype t_flow, wl_dtype t_acc, const wl_grid *g, const void *u, const void *p, const wl_grid *ga, void *U,
                        void *P, void *UU, void *pp, double eps, int first) {
@@ -1657,7 +1605,7 @@ int wl_surface_totals(const double *rows_dev, const double *geom_dev, int64_t nt
     int rc = 0;
     Scratch &S = global_scratch(&rc);
     WL_TRY(rc);
-    return op_surface_totals(rows_dev, geom_dev, nt, x0, S.partials, out_dev);
+    return op_surface_totals(rows_dev, geom_dev, nt, x0, S.partials.get(), out_dev);
 }
 int wl_iso_table(int tet, int mask, int32_t out[7]) {
     if (tet < 0 || tet > 5 || mask < 0 || mask > 15) return fail(WL_E_ARG, "wl_iso_table: tet must lie in 0..5 and mask in 0..15", __FILE__, __LINE__);
@@ -1715,16 +1663,16 @@ int wl_pforce(wl_dtype t, const wl_grid *g, const void *p, const int64_t *idx, c
     if (nb > 0) {
         Prof pr(WL_K_PFORCE, nband);
         if (t == WL_F32)
-            hipLaunchKernelGGL(k_pforce<float>, dim3(nb), dim3(256), 0, ctx().stream, (const float *)p, idx, nds, nband, g->D, S.partials);
+            hipLaunchKernelGGL(k_pforce<float>, dim3(nb), dim3(256), 0, ctx().stream, (const float *)p, idx, nds, nband, g->D, S.partials.get());
         else
-            hipLaunchKernelGGL(k_pforce<double>, dim3(nb), dim3(256), 0, ctx().stream, (const double *)p, idx, nds, nband, g->D, S.partials);
+            hipLaunchKernelGGL(k_pforce<double>, dim3(nb), dim3(256), 0, ctx().stream, (const double *)p, idx, nds, nband, g->D, S.partials.get());
         WL_HIP(hipGetLastError());
     }
-    State *st = S.st;
-    WL_TRY((launch_finalize<3>(gg.dist, S.partials, nb, RED_SUM, 0.0, st->red, [=] __device__(const double *v) {
+    State *st = S.st.get();
+    WL_TRY((launch_finalize<3>(gg.dist, S.partials.get(), nb, RED_SUM, 0.0, st->red, [=] __device__(const double *v) {
         st->out[0] = v[0]; st->out[1] = v[1]; st->out[2] = v[2]; })));
     WL_TRY(S.fetch());
-    for (int c = 0; c < g->D; ++c) out[c] = S.hst->out[c];
+    for (int c = 0; c < g->D; ++c) out[c] = S.hst.get()->out[c];
     return 0;
 }
 
@@ -1789,20 +1737,20 @@ int wl_prof_allreduce_us(int reps, double *us_per_op) {
     int rc = 0;
     Scratch &S = global_scratch(&rc);
     WL_TRY(rc);
-    WL_HIP(hipMemsetAsync(S.partials, 0, sizeof(double) * 64, ctx().stream));
+    WL_HIP(hipMemsetAsync(S.partials.get(), 0, sizeof(double) * 64, ctx().stream));
     hipEvent_t a, b;
     WL_HIP(hipEventCreate(&a));
     WL_HIP(hipEventCreate(&b));
-    for (int w = 0; w < 3 && !rc; ++w) rc = reduce_allreduce<1>(S.partials, 64, RED_SUM, 0.0, S.st->red);   // warm-up
+    for (int w = 0; w < 3 && !rc; ++w) rc = reduce_allreduce<1>(S.partials.get(), 64, RED_SUM, 0.0, S.st.get()->red);   // warm-up
     if (!rc) rc = (int)hipEventRecord(a, ctx().stream);
-    for (int q = 0; q < reps && !rc; ++q) rc = reduce_allreduce<1>(S.partials, 64, RED_SUM, 0.0, S.st->red);
+    for (int q = 0; q < reps && !rc; ++q) rc = reduce_allreduce<1>(S.partials.get(), 64, RED_SUM, 0.0, S.st.get()->red);
     if (!rc) rc = (int)hipEventRecord(b, ctx().stream);
     if (!rc) rc = (int)hipEventSynchronize(b);
     float ms = 0;
     if (!rc) rc = (int)hipEventElapsedTime(&ms, a, b);
     (void)hipEventDestroy(a); (void)hipEventDestroy(b);
     if (rc) return rc < 10000 ? fail(rc, "wl_prof_allreduce_us", __FILE__, __LINE__) : rc;
-    if (ctx().mbox && *ctx().mbox->err_host) return fail(WL_E_STATE, "mailbox all-reduce: gave up waiting for a peer rank", __FILE__, __LINE__);
+    if (ctx().mbox && *ctx().mbox->err_host.get()) return fail(WL_E_STATE, "mailbox all-reduce: gave up waiting for a peer rank", __FILE__, __LINE__);
     *us_per_op = (double)ms * 1e3 / reps;
     return 0;
 }

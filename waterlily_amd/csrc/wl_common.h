@@ -21,8 +21,12 @@
 #include <cstdlib>
 
 #include "../../include/wlhip.h"
+#include "wl_buf.h"
 
 namespace wl {
+
+struct DevMem;                               // the Buf policies (below, next to the counted allocators)
+template <unsigned FLAGS> struct PinnedMem;
 
 // ------------------------------------------------------------------------------------------ context
 struct TimedEvt { hipEvent_t a, b; int64_t cells; };
@@ -65,7 +69,8 @@ struct Mailbox {
     MboxSlot *host = nullptr, *dev = nullptr;   // [2][nranks] slots, host mapping and the device pointer to it
     size_t bytes = 0;
     unsigned long long seq = 0;                 // all-reduces issued so far (identical on every rank: SPMD)
-    int *err_host = nullptr, *err_dev = nullptr;   // set by a kernel that gave up waiting for a peer
+    Buf<int, PinnedMem<hipHostMallocMapped>> err_host;   // set by a kernel that gave up waiting for a peer
+    int *err_dev = nullptr;                              // (the device's address of err_host)
 };
 
 // wl_set_option (names and meaning: include/wlhip.h): THE table of keys and defaults.  A key is live when it has a row;
@@ -115,6 +120,21 @@ inline int opt(int key) { return ctx().opt.v[key]; }   // current value of WL_OP
 inline hipError_t wl_dev_alloc(void **p, size_t n) { ctx().n_alloc += 1; ctx().alloc_bytes += (int64_t)n; return hipMalloc(p, n); }
 inline hipError_t wl_host_alloc(void **p, size_t n, unsigned flags) { ctx().n_alloc += 1; ctx().alloc_bytes += (int64_t)n; return hipHostMalloc(p, n, flags); }
 int fail(int code, const char *what, const char *file, int line);
+// ... as the policies of Buf (wl_buf.h), which owns every block the library allocates; a failure is reported here
+struct DevMem {
+    static int alloc(void **p, size_t bytes) {
+        const hipError_t e = wl_dev_alloc(p, bytes);
+        return e == hipSuccess ? 0 : fail((int)e, "wl_dev_alloc", __FILE__, __LINE__);
+    }
+    static void free(void *p) { (void)hipFree(p); }
+};
+template <unsigned FLAGS> struct PinnedMem {
+    static int alloc(void **p, size_t bytes) {
+        const hipError_t e = wl_host_alloc(p, bytes, FLAGS);
+        return e == hipSuccess ? 0 : fail((int)e, "wl_host_alloc", __FILE__, __LINE__);
+    }
+    static void free(void *p) { (void)hipHostFree(p); }
+};
 
 #define WL_HIP(expr)                                                        \
     do {                                                                    \

@@ -268,18 +268,18 @@ struct wl_mesh {
     int nb[3] = {0, 0, 0};
     int64_t max_per_bin = 0, crossed = 0, nonempty = 0;
     // device copies (created once, by the first call that needs them)
-    mutable double *d_tri = nullptr;
-    mutable int *d_start = nullptr, *d_list = nullptr;
-    mutable signed char *d_sign = nullptr;
+    mutable wl::Buf<double, wl::DevMem> d_tri;
+    mutable wl::Buf<int, wl::DevMem> d_start, d_list;
+    mutable wl::Buf<signed char, wl::DevMem> d_sign;
     size_t device_bytes() const {
         return tri.size() * sizeof(double) + (bin_start.size() + std::max<size_t>(bin_tri.size(), 1)) * sizeof(int) + bin_sign.size();
     }
     wl::MeshDev view(bool device) const {
         wl::MeshDev M;
-        M.tri = device ? d_tri : tri.data();
-        M.bin_start = device ? d_start : bin_start.data();
-        M.bin_tri = device ? d_list : bin_tri.data();
-        M.bin_sign = device ? d_sign : bin_sign.data();
+        M.tri = device ? d_tri.get() : tri.data();
+        M.bin_start = device ? d_start.get() : bin_start.data();
+        M.bin_tri = device ? d_list.get() : bin_tri.data();
+        M.bin_sign = device ? d_sign.get() : bin_sign.data();
         for (int a = 0; a < 3; ++a) { M.lo[a] = lo[a]; M.nb[a] = nb[a]; }
         M.h = h; M.inv_h = 1.0 / h; M.R = R;
         return M;
