@@ -460,6 +460,59 @@ int wl_iso_table(int tet, int mask, int32_t out[7]);
 int wl_isosurface(wl_dtype t, const wl_grid *g, const void *a, const void *b, double c, const int32_t lo[3], const int32_t hi[3],
                   double *tri_dev, double *val_dev, int64_t cap, int64_t *count_dev);
 
+/* ------------------------------------------------------------------ slice and projection images (Renderer, waterlily_amd/render.py)
+ * The on-device twin of the pictures of ext/WaterLilyPlotsExt.jl (flood, body_plot!, sim_gif!: :17-52), without the volume the
+ * reference fills and copies to the host for them.
+ *
+ * wl_render_project reduces the cells lo_d <= J_d < hi_d (0-based) along `axis` to an image of doubles; the value of a cell is
+ * formed on the fly from the field f, converted to double before its first use:
+ *   WL_R_SCALAR           f a scalar field: the element as stored
+ *   WL_R_UCOMP            f a vector field: component ipar as stored, at its face
+ *   WL_R_CENTRE           f a vector field: ((double)f[I,c] + (double)f[I+e_c,c]) / 2, c = ipar
+ *   WL_R_METRIC + WL_M_*  f = u: (double)(T)m, m what wl_metric of that kind stores in cell I (ipar, par, par2 as there; the
+ *                         same device function evaluates both, so the bits are wl_metric's)
+ *   box   : lo == hi == NULL: inside(), lo = 1, hi_d = n_d - 1 (nzg - 1 along z).  Any 0 <= lo_d <= hi_d <= n_d - 1 is allowed
+ *           (wl_isosurface's rule; z is global) for a caller whose ghost cells are current; a metric kind reads a 1-cell
+ *           neighbourhood, so its box must lie in inside().  D == 2: two entries are read.
+ *   image : its axes are the two other than `axis` in ascending order, the lower one fast: pixel (a, b), counted from the
+ *           box's low corner, is img_dev[b*ld + a].  D == 2: axis must be 2, the image is the field and every mode gives the
+ *           same numbers.  A slice is a box one cell thick along `axis`.
+ *   modes : all visit the cells in ascending index along `axis`.  WL_R_MAX, WL_R_MIN: NaN is skipped; WL_R_ABSMAX: the signed
+ *           value of largest magnitude, the first one on a tie, NaN skipped; a ray of these three that holds nothing but NaN (or
+ *           no cell) gives NaN.  WL_R_SUM: a double accumulator that starts at +0 (NaN propagates); WL_R_MEAN: that sum
+ *           divided once by hi_axis - lo_axis.
+ *   order : axis 1 or 2: one accumulator per pixel.  axis 0: lane l of 64 takes the cells lo_0 + l, lo_0 + l + 64, ... in
+ *           ascending order (a lane without a cell holds the start value), then for off = 32, 16, ..., 1: s_l (+)= s_{l+off} over
+ *           the lanes l < off, s_l the earlier operand (on an ABSMAX tie the lower lane stays).  No atomics: a numpy loop in
+ *           this order reproduces the bits (tests/render_ref.py).
+ *   slabs : a rank visits the planes of the box it owns (the first rank of a ring also takes the bottom ghost plane, as for
+ *           wl_isosurface).  axis 0 or 1: z is the image's slow axis; the rank writes the rows of its planes -- row = global z -
+ *           lo_2 -- and touches no other row.  axis 2: a partial image over its planes; MEAN still divides by the undecomposed
+ *           extent, so SUM and MEAN partials add up and MAX / MIN / ABSMAX partials combine in rank order (a rank without a plane
+ *           in the box writes NaN / 0).  A metric kind reads the first halo plane on each side (mom_step! leaves u's current).
+ *           Nothing is communicated.
+ * Refused with WL_E_ARG before the device is touched: NULL g, f or img_dev; an unknown dtype, kind, component or mode; an axis
+ * the dimension does not have (D == 2: any but 2); a bad box; only one of lo and hi; a metric box outside inside(); ld smaller
+ * than the image width.  Asynchronous: one launch on the library's stream, nothing allocated.
+ *
+ * wl_render_shade turns such an image (nx x ny) into RGBA8 through a 256-entry colour table, all in IEEE double:
+ *   t = (v - vmin) / (vmax - vmin);  levels == 0: idx = clamp(floor(t*256), 0, 255);  levels = n > 0 (the bands of a filled
+ *   contour plot): b = clamp(floor(t*n), 0, n-1), idx = floor((b + 0.5) * 256 / n);  the pixel is lut[idx]; a NaN v gives nan_rgba
+ *   (NULL: 0,0,0,0).  With mask_dev (a second image, leading dimension ldm) a pixel whose mask value is < mask_lt gets
+ *   mask_rgba, whatever v is.  Every pixel becomes zoom x zoom output pixels; flip_y puts the image's last row first (the
+ *   high index at the top, as a plot shows it).  rgba_dev: (ny*zoom) x (nx*zoom) x 4 bytes, dense, 4-byte aligned.
+ * lut_dev: 256*4 bytes of device memory; mask_rgba / nan_rgba: host arrays.  Refused with WL_E_ARG: vmin >= vmax or either not
+ * finite; levels < 0 or > 256; zoom < 1; a NULL image, table or output; negative extents or ld < nx; a mask without its
+ * colour or with ldm < nx.  Asynchronous: one launch.  WaterLily v1.3 draws on the host (Plots.jl): both entry points are there
+ * for a later binding. */
+enum { WL_R_SCALAR = 0, WL_R_UCOMP = 1, WL_R_CENTRE = 2, WL_R_METRIC = 16 };
+enum { WL_R_MAX = 0, WL_R_MIN = 1, WL_R_ABSMAX = 2, WL_R_SUM = 3, WL_R_MEAN = 4 };
+int wl_render_project(wl_dtype t, const wl_grid *g, const void *f, int kind, int ipar, const double par[3], const double par2[3],
+                      int axis, int mode, const int32_t lo[3], const int32_t hi[3], double *img_dev, int64_t ld);
+int wl_render_shade(const double *img_dev, int64_t ld, int nx, int ny, double vmin, double vmax, int levels, const uint8_t *lut_dev,
+                    const double *mask_dev, int64_t ldm, double mask_lt, const uint8_t mask_rgba[4], const uint8_t nan_rgba[4], int zoom,
+                    int flip_y, uint8_t *rgba_dev);
+
 /* ------------------------------------------------------------------ snapshots (VTK write / restart,ext/WaterLilyWriteVTKExt.jl:57-66,
  * ext/WaterLilyReadVTKExt.jl:28-45).  The reference copies whole fields to the host (`a.flow.u |> Array`) and permutes the vector
  * components to the front there (components_first, :79).  Here the field's LOCAL planes klo..khi are packed on the device into

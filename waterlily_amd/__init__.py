@@ -2,3 +2,4 @@
 from .body import AutoBody, NoBody, measure, norm2  # noqa: F401
 from .mesh import MeshBody  # noqa: F401
 from .probes import Probes, Tracers, interp  # noqa: F401
+from .render import Renderer  # noqa: F401

@@ -19,6 +19,7 @@
 #include "wl_integrals.h"
 #include "wl_surface.h"
 #include "wl_iso.h"
+#include "wl_render.h"
 
 namespace wl {
 
@@ -522,91 +523,14 @@ static int bdim_full(const G &g, T *u, const T *u0, T *f, const T *V, const T *m
     WL_TRY((op_bdim1<T, D>(g, f, u0, V, dt)));
     return op_bdim2<T, D, 0>(g, u, f, V, mu0, mu1);
 }
-// One Jacobi rotation of a symmetric 3x3 matrix in the (p,q) plane (Golub & Van Loan 8.5): zeroes apq; dp, dq are the two
-// diagonal entries, arp and arq the entries that couple the third index to p and to q.  A theta whose square overflows gives
-// t = 0: apq is then far below an ulp of dq - dp and is dropped.
-__host__ __device__ inline void jacobi_rot(double &dp, double &dq, double &apq, double &arp, double &arq) {
-    if (apq == 0.0) return;
-    const double th = (dq - dp) / (2.0 * apq);
-    const double t = copysign(1.0, th) / (fabs(th) + sqrt(th * th + 1.0));
-    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c, x = arp;
-    dp -= t * apq;
-    dq += t * apq;
-    apq = 0.0;
-    arp = c * x - s * arq;
-    arq = s * x + c * arq;
-}
-// middle eigenvalue of a symmetric 3x3 matrix -- lambda2 = eigvals(Hermitian(S^2+O^2))[2].  Cyclic Jacobi sweeps: every
-// rotation is orthogonal to rounding, so the error stays a few eps * ||A|| however close two eigenvalues lie (solid
-// rotation, plane shear, any axisymmetric region); the trigonometric closed form takes acos(r) at r = +-1 there and keeps
-// only half the digits.  A diagonal matrix takes no rotation: its sorted diagonal comes back exactly.  Cyclic Jacobi
-// converges quadratically: after 4 to 5 sweeps a 3x3 matrix is diagonal to working precision and further rotations change
-// nothing.  The loop leaves early only when every off-diagonal entry is exactly zero (a diagonal input, or underflow), so a
-// generic matrix runs all 8 sweeps: 24 rotations of 2 sqrt and 2 divisions each, per cell, in a post-processing kernel.
-__host__ __device__ inline double sym3_mid_eig(double a00, double a01, double a02, double a11, double a12, double a22) {
-    for (int sweep = 0; sweep < 8 && (a01 != 0.0 || a02 != 0.0 || a12 != 0.0); ++sweep) {
-        jacobi_rot(a00, a11, a01, a02, a12);
-        jacobi_rot(a00, a22, a02, a01, a12);
-        jacobi_rot(a11, a22, a12, a01, a02);
-    }
-    double x = a00, y = a11, z = a22, t;
-    if (x > y) { t = x; x = y; y = t; }
-    if (y > z) { t = y; y = z; z = t; }
-    if (x > y) { t = x; x = y; y = t; }
-    return y;
-}
+// `@inside out[I] = metric(I,u)` (src/Metrics.jl:14-77): the per-cell formula is metric_cell (wl_render.h), shared with
+// wl_render_project, which forms the same values without storing them
 template <class T, int D>
 static int op_metric(const G &g, int kind, T *out, const T *u, int ipar, const double *par, const double *par2) {
     const G gg = g;
-    double p3[3] = {0, 0, 0}, q3[3] = {0, 0, 0};
-    if (par) for (int d = 0; d < D; ++d) p3[d] = par[d];
-    if (par2) for (int d = 0; d < D; ++d) q3[d] = par2[d];
-    const double p0 = p3[0], p1 = p3[1], p2 = p3[2], q0 = q3[0], q1 = q3[1], q2 = q3[2];
+    const MetricPar mp = metric_par(D, par, par2);
     return launch_range(WL_K_MISC, r_inside(g), [=] __device__(int i, int j, int k) {
-        const long I = gg.at(i, j, k);
-        const long S[3] = {gg.s[0], gg.s[1], gg.s[2]};
-        const long SC = gg.sc;
-        auto U = [&](int c, long off) -> T { return u[I + off + (long)c * SC]; };
-        auto dudx = [&](int a, int b) -> T {   // Metrics.jl:28-31
-            if (a == b) return U(a, S[a]) - U(a, 0);
-            return (U(a, S[b]) + U(a, S[b] + S[a]) - U(a, -S[b]) - U(a, -S[b] + S[a])) / (T)4;
-        };
-        T res = 0;
-        if (kind == WL_M_KE) {   // Metrics.jl:20-22
-            const double UU[3] = {p0, p1, p2};
-            double s = 0;   // (Float64 accumulation: exact for the reference's Float64 U, >= its precision for U=0)
-            for (int c = 0; c < D; ++c) { const double v = (double)(T)(U(c, 0) + U(c, S[c])) - 2.0 * UU[c]; s += v * v; }
-            res = (T)(0.125 * s);
-        } else if (kind == WL_M_CURL) {   // Metrics.jl:54: permute((j,k)->d(j,CI(I,k),u), i), backward differences
-            const int a = (ipar + 1) % 3, b = (ipar + 2) % 3;
-            res = (U(b, 0) - U(b, -S[a])) - (U(a, 0) - U(a, -S[b]));
-        } else if (D == 3) {
-            T w[3];
-            for (int c = 0; c < 3; ++c) { const int a = (c + 1) % 3, b = (c + 2) % 3; w[c] = dudx(b, a) - dudx(a, b); }   // Metrics.jl:60
-            if (kind == WL_M_OMAG) {
-                res = (T)sqrt((double)(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]));
-            } else if (kind == WL_M_OTHETA) {   // Metrics.jl:72-76
-                const double x[3] = {(double)i - 0.5 - q0, (double)j - 0.5 - q1, (double)(k + gg.kz0) - 0.5 - q2};
-                const double th[3] = {p1 * x[2] - p2 * x[1], p2 * x[0] - p0 * x[2], p0 * x[1] - p1 * x[0]};
-                const double n = sqrt(th[0] * th[0] + th[1] * th[1] + th[2] * th[2]);
-                res = n <= 2.220446049250313e-16 * n ? (T)0 : (T)((th[0] * (double)w[0] + th[1] * (double)w[1] + th[2] * (double)w[2]) / n);
-            } else {   // lambda2, Metrics.jl:41-45
-                double J[3][3], M[3][3];
-                for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) J[a][b] = (double)dudx(a, b);
-                for (int a = 0; a < 3; ++a)
-                    for (int b = a; b < 3; ++b) {
-                        double m = 0;
-                        for (int c = 0; c < 3; ++c) {
-                            const double sa = 0.5 * (J[a][c] + J[c][a]), sb = 0.5 * (J[c][b] + J[b][c]);
-                            const double oa = 0.5 * (J[a][c] - J[c][a]), ob = 0.5 * (J[c][b] - J[b][c]);
-                            m += sa * sb + oa * ob;
-                        }
-                        M[a][b] = m;
-                    }
-                res = (T)sym3_mid_eig(M[0][0], M[0][1], M[0][2], M[1][1], M[1][2], M[2][2]);
-            }
-        }
-        out[I] = res;
+        out[gg.at(i, j, k)] = metric_cell<T, D>(gg, u, kind, ipar, mp, i, j, k);
     });
 }
 
@@ -1639,6 +1563,56 @@ int wl_isosurface(wl_dtype t, const wl_grid *g, const void *a, const void *b, do
     }
     if (t == WL_F32) return op_isosurface<float>(gg, (const float *)a, (const float *)b, c, l, h, tri_dev, val_dev, cap, count_dev);
     return op_isosurface<double>(gg, (const double *)a, (const double *)b, c, l, h, tri_dev, val_dev, cap, count_dev);
+}
+int wl_render_project(wl_dtype t, const wl_grid *g, const void *f, int kind, int ipar, const double par[3], const double par2[3],
+                      int axis, int mode, const int32_t lo[3], const int32_t hi[3], double *img_dev, int64_t ld) {
+    if (!g || !f || !img_dev) return fail(WL_E_ARG, "wl_render_project: null grid, field or image", __FILE__, __LINE__);
+    WL_TRY(check_grid(g));
+    if (t != WL_F32 && t != WL_F64) return fail(WL_E_ARG, "wl_render_project: unknown dtype", __FILE__, __LINE__);
+    const int D = g->D;
+    const bool metric = kind >= WL_R_METRIC;
+    if (metric) {
+        const int m = kind - WL_R_METRIC;
+        if (m > WL_M_LAMBDA2 || (m >= WL_M_OMAG && D != 3) || (m == WL_M_CURL && (ipar < 0 || ipar > 2)))
+            return fail(WL_E_ARG, "wl_render_project: bad metric kind/component for this dimension", __FILE__, __LINE__);
+    } else if (kind < WL_R_SCALAR || kind > WL_R_CENTRE || (kind != WL_R_SCALAR && (ipar < 0 || ipar >= D))) {
+        return fail(WL_E_ARG, "wl_render_project: bad kind/component for this dimension", __FILE__, __LINE__);
+    }
+    if (mode < WL_R_MAX || mode > WL_R_MEAN) return fail(WL_E_ARG, "wl_render_project: bad mode", __FILE__, __LINE__);
+    if (D == 2 ? axis != 2 : (axis < 0 || axis > 2)) return fail(WL_E_ARG, "wl_render_project: bad axis (0..2; a 2-D grid takes 2)", __FILE__, __LINE__);
+    if ((lo != nullptr) != (hi != nullptr)) return fail(WL_E_ARG, "wl_render_project: only one of lo and hi given", __FILE__, __LINE__);
+    const G gg = mkG(g);
+    int l[3] = {0, 0, 0}, h[3] = {1, 1, 1};
+    for (int d = 0; d < D; ++d) {
+        const int n = d == 2 ? gg.nzg : gg.n[d];
+        l[d] = lo ? lo[d] : 1;
+        h[d] = hi ? hi[d] : n - 1;
+        if (!(0 <= l[d] && l[d] <= h[d] && h[d] <= n - 1))
+            return fail(WL_E_ARG, "wl_render_project: bad box (0 <= lo <= hi <= n - 1 in every direction)", __FILE__, __LINE__);
+        if (metric && l[d] < 1) return fail(WL_E_ARG, "wl_render_project: the box of a metric kind must lie in inside()", __FILE__, __LINE__);
+    }
+    if (metric && gg.dist && (gg.zlo < 1 || gg.zhi > gg.n[2] - 2))
+        return fail(WL_E_ARG, "wl_render_project: a metric kind on a z-slab needs a halo plane on each side", __FILE__, __LINE__);
+    const int wa = axis == 0 ? 1 : 0;
+    if (ld < (int64_t)(h[wa] - l[wa])) return fail(WL_E_ARG, "wl_render_project: ld smaller than the image width", __FILE__, __LINE__);
+    WL_DISPATCH(t, D, (op_render_project<T, DD>(gg, (const T *)f, kind, ipar, par, par2, axis, mode, l, h, img_dev, ld)));
+}
+int wl_render_shade(const double *img_dev, int64_t ld, int nx, int ny, double vmin, double vmax, int levels, const uint8_t *lut_dev,
+                    const double *mask_dev, int64_t ldm, double mask_lt, const uint8_t mask_rgba[4], const uint8_t nan_rgba[4], int zoom,
+                    int flip_y, uint8_t *rgba_dev) {
+    if (!img_dev || !lut_dev || !rgba_dev) return fail(WL_E_ARG, "wl_render_shade: null image, colour table or output", __FILE__, __LINE__);
+    if (((uintptr_t)rgba_dev & 3u) != 0) return fail(WL_E_ARG, "wl_render_shade: the output must be 4-byte aligned", __FILE__, __LINE__);
+    if (!(std::isfinite(vmin) && std::isfinite(vmax) && vmin < vmax)) return fail(WL_E_ARG, "wl_render_shade: need finite vmin < vmax", __FILE__, __LINE__);
+    if (levels < 0 || levels > 256) return fail(WL_E_ARG, "wl_render_shade: levels must lie in 0..256", __FILE__, __LINE__);
+    if (zoom < 1) return fail(WL_E_ARG, "wl_render_shade: zoom must be >= 1", __FILE__, __LINE__);
+    if (nx < 0 || ny < 0 || ld < nx) return fail(WL_E_ARG, "wl_render_shade: bad image extents or ld smaller than the width", __FILE__, __LINE__);
+    if (mask_dev && (!mask_rgba || ldm < nx || std::isnan(mask_lt)))
+        return fail(WL_E_ARG, "wl_render_shade: a mask needs its colour, a threshold and ldm >= the width", __FILE__, __LINE__);
+    auto word = [](const uint8_t *c) { return c ? (uint32_t)c[0] | ((uint32_t)c[1] << 8) | ((uint32_t)c[2] << 16) | ((uint32_t)c[3] << 24) : 0u; };
+    ShadeArgs A;
+    A.ld = ld; A.ldm = ldm; A.nx = nx; A.ny = ny; A.levels = levels; A.zoom = zoom; A.flip_y = flip_y ? 1 : 0; A.masked = mask_dev ? 1 : 0;
+    A.vmin = vmin; A.vmax = vmax; A.mask_lt = mask_lt; A.mask_rgba = mask_dev ? word(mask_rgba) : 0u; A.nan_rgba = word(nan_rgba);
+    return op_render_shade(A, img_dev, mask_dev, lut_dev, rgba_dev);
 }
 int wl_tracer_advance(wl_dtype t, const wl_grid *g, const void *u, double *x_dev, int64_t m, double dt, int perdir_mask) {
     WL_TRY(check_grid(g));
