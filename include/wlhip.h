@@ -513,6 +513,50 @@ int wl_render_shade(const double *img_dev, int64_t ld, int nx, int ny, double vm
                     const double *mask_dev, int64_t ldm, double mask_lt, const uint8_t mask_rgba[4], const uint8_t nan_rgba[4], int zoom,
                     int flip_y, uint8_t *rgba_dev);
 
+/* ------------------------------------------------------------------ box-filtered, cropped volumes (Downsampler, waterlily_amd/downsample.py)
+ * The 3-D counterpart of wl_render_project: the fine cells lo_d <= J_d < hi_d (0-based, z global) are cut into blocks of
+ * factor^D cells and every block becomes one coarse cell, its value formed on the fly from f.  No volume is filled first: a
+ * downsampled metric reads u once and stores 1/factor^D of a field.
+ *   kind  : WL_R_SCALAR, WL_R_UCOMP, WL_R_CENTRE, WL_R_METRIC + WL_M_* with ipar, par, par2 exactly as for wl_render_project (the
+ *           same device function forms the value).  WL_R_FACE: f a vector field; the f^(D-1) fine faces of component ipar on the
+ *           low ipar-face of the block, f[J, ipar] as stored: one fine layer along ipar is read, not f of them.  The coarse
+ *           field of MEAN face values is staggered like the fine one, and its divergence over a coarse cell is f^(1-D) times the
+ *           sum of the fine divergences of the block: every interior fine face cancels.
+ *   box   : lo == hi == NULL: inside().  0 <= lo_d < hi_d <= n_d - 1 (nzg - 1 along z) and every extent a multiple of factor; a
+ *           metric kind's box must lie in inside().  D == 2: two entries are read, blocks are f x f.  factor: 1, 2, 4, 8 or 16;
+ *           factor 1 is a crop (with a metric kind: the metric of the box, packed, without a scratch field).
+ *   modes : WL_R_MAX, WL_R_MIN, WL_R_ABSMAX, WL_R_SUM, WL_R_MEAN combine with wl_render_project's rule acc (+)= v (NaN skipped by the
+ *           first three, the first of two equal candidates stays, a block of nothing but NaN gives NaN; SUM and MEAN: a double
+ *           sum from +0, NaN propagates).  MEAN multiplies the sum once by the exact power of two 1/f^D (WL_R_FACE: 1/f^(D-1)).
+ *           WL_R_SAMPLE: the value of the block's first cell (plain decimation).
+ *   order : 64 consecutive fine x of a block row, counted from lo_0, belong to one wavefront; factor divides 64, so a coarse cell
+ *           never straddles two.  The lane of fine x walks the f x f rows of its column of the block, z outer and y inner, both
+ *           ascending, with one accumulator that starts at +0 (SUM, MEAN) or NaN = "nothing yet".  Then the f lanes of a coarse
+ *           cell are combined: for off = f/2, ..., 1: s_l (+)= s_{l+off} over the lanes l < off of the block, s_l the earlier
+ *           operand; the result is s_0.  WL_R_FACE visits the low face alone: ipar == 0: only lane 0 of the block walks (the
+ *           others enter the tree with the start value); ipar == 1: the first y row of the block; ipar == 2: its first z plane.
+ *           No atomics: a numpy loop in this order reproduces the bits (tests/downsample_ref.py).
+ *   out   : dense, x fast: coarse cell (I, J, K), counted from the box's low corner (K from this rank's first coarse plane),
+ *           goes to out_dev[((K*ncy + J)*ncx + I)*ntuple + c] as t_out (WL_F32 or WL_F64): the double result is rounded once,
+ *           at the store.  Entries of other c are not touched, so the components of a vector interleave into one staging buffer
+ *           the way wl_snapshot_pack lays them out.  1 <= ntuple <= 9, 0 <= c < ntuple.
+ *   slabs : a rank emits the blocks that lie wholly within the planes it owns (the first rank of a ring also takes the bottom
+ *           ghost plane, as for wl_isosurface); a boundary of its planes that falls inside the box must be at lo_2 + m*factor,
+ *           else WL_E_ARG.  The ranks' outputs concatenated in rank order are the undecomposed output bit for bit; nothing is
+ *           communicated.  A metric kind reads the first halo plane on each side, WL_R_CENTRE along z the one above.
+ * wl_downsample_extent (host arithmetic only) gives this rank's coarse extents nc (D == 2: nc[2] = 1) and its first coarse
+ * plane k0 for a box: what a caller sizes its buffer with and places the part by.  It applies the factor, box and slab checks.
+ * Refused with WL_E_ARG before the device is touched: NULL g, f or out_dev; an unknown t, t_out, kind, component or mode; a
+ * factor outside the set; extents that are no multiples of it; only one of lo and hi; a bad box; a metric box outside inside();
+ * ntuple or c out of range; WL_R_FACE without a vector component (ipar outside 0..D-1).  Asynchronous: one launch on the
+ * library's stream, no LDS, nothing allocated.  wl_render_project refuses WL_R_FACE and WL_R_SAMPLE.  WaterLily v1.3 has no
+ * such function to override. */
+enum { WL_R_FACE = 3 };
+enum { WL_R_SAMPLE = 5 };
+int wl_downsample(wl_dtype t, const wl_grid *g, const void *f, int kind, int ipar, const double par[3], const double par2[3],
+                  int mode, int factor, const int32_t lo[3], const int32_t hi[3], wl_dtype t_out, void *out_dev, int ntuple, int c);
+int wl_downsample_extent(const wl_grid *g, int factor, const int32_t lo[3], const int32_t hi[3], int32_t nc[3], int32_t *k0);
+
 /* ------------------------------------------------------------------ snapshots (VTK write / restart,ext/WaterLilyWriteVTKExt.jl:57-66,
  * ext/WaterLilyReadVTKExt.jl:28-45).  The reference copies whole fields to the host (`a.flow.u |> Array`) and permutes the vector
  * components to the front there (components_first, :79).  Here the field's LOCAL planes klo..khi are packed on the device into

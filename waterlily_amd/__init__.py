@@ -1,5 +1,6 @@
 """waterlily_amd -- MI355X-native backend for WaterLily's `sim_step!` hot path."""
 from .body import AutoBody, NoBody, measure, norm2  # noqa: F401
+from .downsample import Downsampler, DownsampleWriter  # noqa: F401
 from .mesh import MeshBody  # noqa: F401
 from .probes import Probes, Tracers, interp  # noqa: F401
 from .render import Renderer  # noqa: F401

@@ -224,6 +224,8 @@ def lib() -> C.CDLL:
         "wl_isosurface": (i, [i, gp, vp, vp, d, C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, vp, i64, vp]),
         "wl_render_project": (i, [i, gp, vp, i, i, dp, dp, i, i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, i64]),
         "wl_render_shade": (i, [vp, i64, i, i, d, d, i, vp, vp, i64, d, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), i, i, vp]),
+        "wl_downsample": (i, [i, gp, vp, i, i, dp, dp, i, i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), i, vp, i, i]),
+        "wl_downsample_extent": (i, [gp, i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
         "wl_snapshot_pack": (i, [i, gp, vp, i, i, i, i, vp]),
         "wl_snapshot_unpack": (i, [i, gp, vp, i, i, i, i, vp]),
         "wl_set_option": (i, [i, i]),

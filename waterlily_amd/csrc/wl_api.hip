@@ -20,6 +20,7 @@
 #include "wl_surface.h"
 #include "wl_iso.h"
 #include "wl_render.h"
+#include "wl_downsample.h"
 
 namespace wl {
 
@@ -1613,6 +1614,69 @@ int wl_render_shade(const double *img_dev, int64_t ld, int nx, int ny, double vm
     A.ld = ld; A.ldm = ldm; A.nx = nx; A.ny = ny; A.levels = levels; A.zoom = zoom; A.flip_y = flip_y ? 1 : 0; A.masked = mask_dev ? 1 : 0;
     A.vmin = vmin; A.vmax = vmax; A.mask_lt = mask_lt; A.mask_rgba = mask_dev ? word(mask_rgba) : 0u; A.nan_rgba = word(nan_rgba);
     return op_render_shade(A, img_dev, mask_dev, lut_dev, rgba_dev);
+}
+// the checks wl_downsample and wl_downsample_extent share: factor and box -> l, h (GLOBAL; D == 2: l[2] = 0, h[2] = 1)
+static int downsample_box(const char *who, const wl_grid *g, const G &gg, int factor, const int32_t lo[3], const int32_t hi[3], int l[3], int h[3]) {
+    char msg[160];
+    auto bad = [&](const char *what) { snprintf(msg, sizeof msg, "%s: %s", who, what); return fail(WL_E_ARG, msg, __FILE__, __LINE__); };
+    if (factor != 1 && factor != 2 && factor != 4 && factor != 8 && factor != 16) return bad("bad factor (1, 2, 4, 8 or 16)");
+    if ((lo != nullptr) != (hi != nullptr)) return bad("only one of lo and hi given");
+    l[0] = l[1] = l[2] = 0;
+    h[0] = h[1] = h[2] = 1;
+    for (int d = 0; d < g->D; ++d) {
+        const int n = d == 2 ? gg.nzg : gg.n[d];
+        l[d] = lo ? lo[d] : 1;
+        h[d] = hi ? hi[d] : n - 1;
+        if (!(0 <= l[d] && l[d] < h[d] && h[d] <= n - 1)) return bad("bad box (0 <= lo < hi <= n - 1 in every direction)");
+        if ((h[d] - l[d]) % factor != 0) return bad("the extents hi - lo of the box must be multiples of factor");
+    }
+    return 0;
+}
+int wl_downsample_extent(const wl_grid *g, int factor, const int32_t lo[3], const int32_t hi[3], int32_t nc[3], int32_t *k0) {
+    if (!g || !nc || !k0) return fail(WL_E_ARG, "wl_downsample_extent: null grid, nc or k0", __FILE__, __LINE__);
+    WL_TRY(check_grid(g));
+    const G gg = mkG(g);
+    int l[3], h[3], n[3], kk, klo;
+    WL_TRY(downsample_box("wl_downsample_extent", g, gg, factor, lo, hi, l, h));
+    if (!down_extent(gg, factor, l, h, n, &kk, &klo))
+        return fail(WL_E_ARG, "wl_downsample_extent: a boundary of this rank's planes inside the box is not at lo_2 + m*factor", __FILE__, __LINE__);
+    nc[0] = n[0]; nc[1] = n[1]; nc[2] = n[2];
+    *k0 = kk;
+    return 0;
+}
+int wl_downsample(wl_dtype t, const wl_grid *g, const void *f, int kind, int ipar, const double par[3], const double par2[3], int mode,
+                  int factor, const int32_t lo[3], const int32_t hi[3], wl_dtype t_out, void *out_dev, int ntuple, int c) {
+    if (!g || !f || !out_dev) return fail(WL_E_ARG, "wl_downsample: null grid, field or output", __FILE__, __LINE__);
+    WL_TRY(check_grid(g));
+    if (t != WL_F32 && t != WL_F64) return fail(WL_E_ARG, "wl_downsample: unknown dtype t", __FILE__, __LINE__);
+    if (t_out != WL_F32 && t_out != WL_F64) return fail(WL_E_ARG, "wl_downsample: unknown dtype t_out", __FILE__, __LINE__);
+    const int D = g->D;
+    const bool metric = kind >= WL_R_METRIC;
+    if (metric) {
+        const int m = kind - WL_R_METRIC;
+        if (m > WL_M_LAMBDA2 || (m >= WL_M_OMAG && D != 3) || (m == WL_M_CURL && (ipar < 0 || ipar > 2)))
+            return fail(WL_E_ARG, "wl_downsample: bad metric kind/component for this dimension", __FILE__, __LINE__);
+    } else if (kind == WL_R_FACE) {
+        if (ipar < 0 || ipar >= D)
+            return fail(WL_E_ARG, "wl_downsample: WL_R_FACE averages component ipar of a vector field (0 <= ipar < D), not a scalar", __FILE__, __LINE__);
+    } else if (kind < WL_R_SCALAR || kind > WL_R_CENTRE || (kind != WL_R_SCALAR && (ipar < 0 || ipar >= D))) {
+        return fail(WL_E_ARG, "wl_downsample: bad kind/component for this dimension", __FILE__, __LINE__);
+    }
+    if (mode < WL_R_MAX || mode > WL_R_SAMPLE) return fail(WL_E_ARG, "wl_downsample: bad mode", __FILE__, __LINE__);
+    if (ntuple < 1 || ntuple > 9) return fail(WL_E_ARG, "wl_downsample: bad ntuple (1 <= ntuple <= 9)", __FILE__, __LINE__);
+    if (c < 0 || c >= ntuple) return fail(WL_E_ARG, "wl_downsample: bad c (0 <= c < ntuple)", __FILE__, __LINE__);
+    const G gg = mkG(g);
+    int l[3], h[3], nc[3], k0, klo;
+    WL_TRY(downsample_box("wl_downsample", g, gg, factor, lo, hi, l, h));
+    if (metric)
+        for (int d = 0; d < D; ++d)
+            if (l[d] < 1) return fail(WL_E_ARG, "wl_downsample: the box of a metric kind must lie in inside()", __FILE__, __LINE__);
+    if (metric && gg.dist && (gg.zlo < 1 || gg.zhi > gg.n[2] - 2))
+        return fail(WL_E_ARG, "wl_downsample: a metric kind on a z-slab needs a halo plane on each side", __FILE__, __LINE__);
+    if (!down_extent(gg, factor, l, h, nc, &k0, &klo))
+        return fail(WL_E_ARG, "wl_downsample: a boundary of this rank's planes inside the box is not at lo_2 + m*factor", __FILE__, __LINE__);
+    l[2] = klo;
+    WL_DISPATCH(t, D, (op_downsample<T, DD>(gg, (const T *)f, kind, ipar, par, par2, mode, factor, l, nc, t_out == WL_F64, out_dev, ntuple, c)));
 }
 int wl_tracer_advance(wl_dtype t, const wl_grid *g, const void *u, double *x_dev, int64_t m, double dt, int perdir_mask) {
     WL_TRY(check_grid(g));

@@ -206,6 +206,30 @@ def _pvti(wext, arrays, pieces) -> bytes:
     return "\n".join(out).encode()
 
 
+def _take_slot(w: VTKWriter, nbytes: int, device, zero: bool = False) -> Optional[_Slot]:
+    """The device staging slot of the next snapshot, at least `nbytes` large, marked busy, with the worker running; None when
+    on_busy == "skip" dropped the snapshot.  zero: a newly made slot starts as zeros (a writer that leaves padding untouched)."""
+    slot = w._slots[w.count % len(w._slots)]
+    if not slot.free.is_set():
+        if w.on_busy == "skip":
+            w.stats["skipped"] += 1
+            w.count += 1
+            return None
+        t1 = _time.perf_counter()
+        slot.free.wait()
+        w.stats["wait_s"] += _time.perf_counter() - t1
+        w._check()
+    slot.free.clear()
+    if slot.buf is None or slot.buf.numel() < nbytes:
+        # sized once: every slot of the ring at the first snapshot (an allocation synchronises the device -- none later)
+        torch.cuda.synchronize()
+        for s in w._slots:
+            if s is slot or s.free.is_set():
+                s.buf = (torch.zeros if zero else torch.empty)(nbytes, dtype=torch.uint8, device=device)
+    w._start(device)
+    return slot
+
+
 def write(w: VTKWriter, sim) -> None:
     """WriteVTKExt.jl:57-66: snapshot at sim_time(sim).  Returns as soon as the pack kernels are enqueued (see the module text)."""
     w._check()
@@ -231,24 +255,9 @@ def write(w: VTKWriter, sim) -> None:
         n = N[0] * N[1] * npl * nct * tsz
         fields.append((name, a, nc, nct, nbytes, n))
         nbytes += (n + 255) // 256 * 256
-    slot = w._slots[w.count % len(w._slots)]
-    if not slot.free.is_set():
-        if w.on_busy == "skip":
-            w.stats["skipped"] += 1
-            w.count += 1
-            return
-        t1 = _time.perf_counter()
-        slot.free.wait()
-        w.stats["wait_s"] += _time.perf_counter() - t1
-        w._check()
-    slot.free.clear()
-    if slot.buf is None or slot.buf.numel() < nbytes:
-        # sized once: every slot of the ring at the first snapshot (an allocation synchronises the device -- none later)
-        torch.cuda.synchronize()
-        for s in w._slots:
-            if s is slot or s.free.is_set():
-                s.buf = torch.empty(nbytes, dtype=torch.uint8, device=flow.device)
-    w._start(flow.device)
+    slot = _take_slot(w, nbytes, flow.device)
+    if slot is None:
+        return
     for name, a, nc, nct, off, n in fields:
         g = S._grid_of(a, D)
         _lib.check(L.wl_snapshot_pack(S._WLT[T], C.byref(g), C.c_void_p(a.data_ptr()), nc, nct, klo if D == 3 else 0,
