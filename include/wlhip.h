@@ -331,6 +331,49 @@ int wl_vforce(wl_dtype t, const wl_grid *g, const void *u, const int64_t *idx_de
 int wl_pmoment(wl_dtype t, const wl_grid *g, const void *p, const int64_t *idx_dev, const double *nds_dev, int64_t nband,
                const double x0[3], double out[3]);
 
+/* ------------------------------------------------------------------ body loads (Forces, waterlily_amd/forces.py)
+ * Force, moment and power of the fluid on a body in ONE sweep over a list of n band cells, nds(body, loc(0,I), t) =
+ * n * kern(clamp(d,-1,1)) (src/Metrics.jl:84-87, body_measure with fastd2 = 1) evaluated in registers.  rows_dev (device
+ * memory) receives nleaf + 1 rows of 16 doubles: rows 0 .. nleaf-1 the leaves of a composite, row nleaf the total.
+ * Per counted cell I, T = the flow's type, everything else Float64:
+ *   fp[c] = Float64( T( p[I] * nds[c] ) )                                              the term of wl_pforce
+ *   fv[c] = Float64( T( sum_j Float64( T( -nu * (d(c,j) + d(j,c)) ) ) * nds[j] ) )     the term of wl_vforce, d = ∂(i,j,I,u)
+ *   r     = loc(0,I) - x0    (z-slabs: the global z)         V = the body's velocity at loc(0,I) (AutoBody.jl:128-130)
+ * and every column is the plain sum over the cells of the row:
+ *   0-2  Fp = fp        3-5  Fv = fv        6-8  Mp = r x fp    9-11 Mv = r x fv    (double arithmetic on the rounded fp, fv)
+ *   12   Wp = fp . V    13   Wv = fv . V    the rate of work of the fluid's load at the body's velocity
+ *   14   ncells         15   A = |nds|      counted cells; the surface-measure estimate (area, D == 2: perimeter)
+ * D == 2: the z slots of Fp, Fv and the x, y slots of Mp, Mv are 0; the scalar moment r_x f_y - r_y f_x is in slot z (cols 8,
+ *   11).  wl_pmoment differs: it writes the scalar into both of its two slots, like the reference's broadcast, and rounds
+ *   T(p * (r x nds)) where this rounds fp first.
+ * Counted: a cell some component of whose nds is non-zero, i.e. kern(clamp(d)) != 0 with a defined normal -- the cells the
+ *   compaction of the composed path (wl_body_nds, then dropping the zero vectors) hands to wl_pforce.  Any other cell is
+ *   left before p or u is read: a NaN outside the band |d| < 1 does not enter.  A NaN in p at a counted cell makes NaN in
+ *   the sums it enters (Fp, Mp, Wp of that cell's leaf and of the total) and nowhere else; likewise u (Fv, Mv, Wv).
+ * Leaves: row q holds the cells whose ACTIVE leaf at the cell centre is q (wl_body_desc: the leaf that supplies distance,
+ *   normal and velocity).  For a union of disjoint bodies that is the load on each body; across WL_BODY_OP_MINUS /
+ *   _INTERSECT it is only an attribution of surface patches.  Row nleaf = row 0 + row 1 + .. in ascending order, so the
+ *   total is reproducible from the leaf rows bit for bit.  nleaf = body[0].count (0 read as 1); 1 for a mesh or a stored band.
+ * Sources:  wl_body_loads: a parametric body / composite, D = 2 or 3; cand_dev = LOCAL dense column-major cell indices as
+ *   written by wl_measure_fill.  wl_body_loads_mesh: a triangle mesh and its pose (D == 3), the same list.  wl_band_loads: a
+ *   stored band as for wl_pforce -- idx_dev element offsets, nds_dev[b*D + c] -- for bodies the device cannot evaluate; it
+ *   carries no V, so cols 12 and 13 of both rows are NaN (also when n == 0).  Entries that are not cells of inside(p) are
+ *   not counted.
+ * z-slabs: a rank counts a candidate only if its plane is owned and globally interior; nothing is communicated, every column
+ *   is additive over the ranks (ncells included).
+ * Order: each thread walks its cells grid-strided in ascending list order, one masked pass per leaf; wavefront, workgroup,
+ *   then one final workgroup sums the workgroups' partials in ascending order.  No floating-point atomics: the same inputs
+ *   give the same bits on every call.  n == 0 reads no list and writes zero rows (ncells = 0).
+ * Asynchronous: two launches on the library's stream, nothing allocated after the library's first reduction, no
+ * synchronisation.  Null pointers, n < 0, D other than 2 / 3, a mesh with D != 3 and count > WL_BODY_MAXLEAF return WL_E_ARG
+ * before any device call.  WaterLily v1.3 has no such function to override: the entry points are there for a later binding. */
+int wl_body_loads(wl_dtype t, const wl_grid *g, const void *p, const void *u, double nu, const wl_body_desc *body,
+                  const int64_t *cand_dev, int64_t n, const double x0[3], double *rows_dev /* (count+1)*16 */);
+int wl_body_loads_mesh(wl_dtype t, const wl_grid *g, const void *p, const void *u, double nu, const wl_mesh *m,
+                       const wl_mesh_pose *pose, const int64_t *cand_dev, int64_t n, const double x0[3], double *rows_dev /* 2*16 */);
+int wl_band_loads(wl_dtype t, const wl_grid *g, const void *p, const void *u, double nu, const int64_t *idx_dev,
+                  const double *nds_dev, int64_t n, const double x0[3], double *rows_dev /* 2*16 */);
+
 /* Field metrics over inside(out) (src/Metrics.jl:14-77), `@inside out[I] = metric(I,u)`:
  *   WL_M_KE      ke(I,u,U)            0.125*sum_i (u[I,i]+u[I+d_i,i]-2U_i)^2          (par = U)
  *   WL_M_CURL    curl(i,I,u)          component i=ipar of curl u at the cell EDGE      (D==2: i=3 -> ipar=2)

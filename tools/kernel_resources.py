@@ -46,6 +46,10 @@ def short(d):
         m = re.match(r"(?:float|double), (\d+), (true|false)", args)
         if m:
             extra = [f"NRED={m.group(1)}", "rowconst" if m.group(2) == "true" else ""]
+    elif kern == "k_loads":
+        m = re.match(r"(?:float|double), (\d), (Loads\w+)", args)
+        if m:
+            extra = [f"D={m.group(1)}", m.group(2)]
     elif kern.startswith("k_convdiff3s"):
         m = re.match(r"(?:float|double), (true|false), (true|false), (\d+)", args)
         if m:

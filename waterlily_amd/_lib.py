@@ -214,6 +214,9 @@ def lib() -> C.CDLL:
         "wl_pforce": (i, [i, gp, vp, vp, vp, i64, dp]),
         "wl_vforce": (i, [i, gp, vp, vp, vp, i64, d, dp]),
         "wl_pmoment": (i, [i, gp, vp, vp, vp, i64, dp, dp]),
+        "wl_body_loads": (i, [i, gp, vp, vp, d, C.POINTER(BodyDesc), vp, i64, dp, vp]),
+        "wl_body_loads_mesh": (i, [i, gp, vp, vp, d, vp, C.POINTER(MeshPose), vp, i64, dp, vp]),
+        "wl_band_loads": (i, [i, gp, vp, vp, d, vp, vp, i64, dp, vp]),
         "wl_flow_integrals": (i, [i, gp, vp, dp, vp]),
         "wl_meanflow_update": (i, [i, i, gp, vp, vp, gp, vp, vp, vp, vp, d, i]),
         "wl_interp": (i, [i, gp, vp, i, vp, i64, vp, i64]),

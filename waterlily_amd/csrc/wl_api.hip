@@ -17,6 +17,7 @@
 #include "wl_stats.h"
 #include "wl_probe.h"
 #include "wl_integrals.h"
+#include "wl_forces.h"
 #include "wl_surface.h"
 #include "wl_iso.h"
 #include "wl_render.h"
@@ -1451,6 +1452,64 @@ int wl_pmoment(wl_dtype t, const wl_grid *g, const void *p, const int64_t *idx, 
         if (t == WL_F32) hipLaunchKernelGGL(k_pmoment<float>, dim3(nb), dim3(256), 0, ctx().stream, gg, (const float *)p, idx, nds, nband, a, b, c, S.partials.get());
         else hipLaunchKernelGGL(k_pmoment<double>, dim3(nb), dim3(256), 0, ctx().stream, gg, (const double *)p, idx, nds, nband, a, b, c, S.partials.get());
     });
+}
+// ---- Forces (wl_forces.h): every argument check comes before the first device call
+static int check_loads(const char *who, wl_dtype t, const wl_grid *g, const void *p, const void *u, const void *list, int64_t n,
+                       const double *x0, const double *rows) {
+    const std::string w(who);
+    if (!g || !p || !u || !x0 || !rows) return fail(WL_E_ARG, (w + ": null grid, p, u, x0 or rows").c_str(), __FILE__, __LINE__);
+    if (t != WL_F32 && t != WL_F64) return fail(WL_E_ARG, (w + ": unknown dtype").c_str(), __FILE__, __LINE__);
+    if (n < 0) return fail(WL_E_ARG, (w + ": n < 0").c_str(), __FILE__, __LINE__);
+    if (n > 0 && !list) return fail(WL_E_ARG, (w + ": null cell list").c_str(), __FILE__, __LINE__);
+    if (g->D != 2 && g->D != 3) return fail(WL_E_ARG, (w + ": D must be 2 or 3").c_str(), __FILE__, __LINE__);
+    WL_TRY(check_grid(g));
+    const G gg = mkG(g);
+    const Range R = r_inside(gg);
+    if (g->D == 3 && R.count() > 0 && (R.lo[2] < 1 || R.hi[2] > gg.n[2] - 2))
+        return fail(WL_E_ARG, (w + ": an owned interior plane without a halo plane on each side").c_str(), __FILE__, __LINE__);
+    return 0;
+}
+int wl_body_loads(wl_dtype t, const wl_grid *g, const void *p, const void *u, double nu, const wl_body_desc *body, const int64_t *cand_dev,
+                  int64_t n, const double x0[3], double *rows_dev) {
+    WL_TRY(check_loads("wl_body_loads", t, g, p, u, cand_dev, n, x0, rows_dev));
+    WL_TRY(check_body(body, g->D));
+    WL_GS();
+    const int nleaf = body[0].count > 0 ? body[0].count : 1;
+    if (g->D == 3) {
+        const LoadsBody<3> src{body_dev(body), (const long *)cand_dev};
+        if (t == WL_F32) return op_loads<float, 3>(gg, src, (const float *)p, (const float *)u, nu, (long)n, x0, nleaf, S.partials.get(), rows_dev);
+        return op_loads<double, 3>(gg, src, (const double *)p, (const double *)u, nu, (long)n, x0, nleaf, S.partials.get(), rows_dev);
+    }
+    const LoadsBody<2> src{body_dev(body), (const long *)cand_dev};
+    if (t == WL_F32) return op_loads<float, 2>(gg, src, (const float *)p, (const float *)u, nu, (long)n, x0, nleaf, S.partials.get(), rows_dev);
+    return op_loads<double, 2>(gg, src, (const double *)p, (const double *)u, nu, (long)n, x0, nleaf, S.partials.get(), rows_dev);
+}
+int wl_body_loads_mesh(wl_dtype t, const wl_grid *g, const void *p, const void *u, double nu, const wl_mesh *m, const wl_mesh_pose *pose,
+                       const int64_t *cand_dev, int64_t n, const double x0[3], double *rows_dev) {
+    WL_TRY(check_loads("wl_body_loads_mesh", t, g, p, u, cand_dev, n, x0, rows_dev));
+    if (g->D != 3) return fail(WL_E_ARG, "wl_body_loads_mesh: a triangle mesh needs D == 3", __FILE__, __LINE__);
+    LoadsMesh src;
+    WL_TRY(mesh_pose(m, pose, 1.0, src.P));
+    WL_GS();
+    WL_TRY(mesh_upload(m));
+    src.M = m->view(true);
+    src.cand = (const long *)cand_dev;
+    if (t == WL_F32) return op_loads<float, 3>(gg, src, (const float *)p, (const float *)u, nu, (long)n, x0, 1, S.partials.get(), rows_dev);
+    return op_loads<double, 3>(gg, src, (const double *)p, (const double *)u, nu, (long)n, x0, 1, S.partials.get(), rows_dev);
+}
+int wl_band_loads(wl_dtype t, const wl_grid *g, const void *p, const void *u, double nu, const int64_t *idx_dev, const double *nds_dev,
+                  int64_t n, const double x0[3], double *rows_dev) {
+    WL_TRY(check_loads("wl_band_loads", t, g, p, u, idx_dev, n, x0, rows_dev));
+    if (n > 0 && !nds_dev) return fail(WL_E_ARG, "wl_band_loads: null nds", __FILE__, __LINE__);
+    WL_GS();
+    if (g->D == 3) {
+        const LoadsBand<3> src{idx_dev, nds_dev};
+        if (t == WL_F32) return op_loads<float, 3>(gg, src, (const float *)p, (const float *)u, nu, (long)n, x0, 1, S.partials.get(), rows_dev);
+        return op_loads<double, 3>(gg, src, (const double *)p, (const double *)u, nu, (long)n, x0, 1, S.partials.get(), rows_dev);
+    }
+    const LoadsBand<2> src{idx_dev, nds_dev};
+    if (t == WL_F32) return op_loads<float, 2>(gg, src, (const float *)p, (const float *)u, nu, (long)n, x0, 1, S.partials.get(), rows_dev);
+    return op_loads<double, 2>(gg, src, (const double *)p, (const double *)u, nu, (long)n, x0, 1, S.partials.get(), rows_dev);
 }
 int wl_metric(wl_dtype t, const wl_grid *g, int kind, void *out, const void *u, int ipar, const double par[3],
               const double par2[3]) {

@@ -112,12 +112,14 @@ template <int D> __device__ __forceinline__ double body_sdf(const BodyDev &B, co
     return body_sdf<D>(B, x, act, sgn);
 }
 // measure(body, x, t; fastd2)  src/AutoBody.jl:115-131 (for `Bodies`: :107-110 -- measure of the active leaf's sdf and map)
+// act: the active leaf at x (also when the point is beyond fastd2)
 template <int D>
-__device__ __forceinline__ void body_measure(const BodyDev &BB, const double (&x)[D], double fastd2, double &d, double (&n)[D], double (&V)[D]) {
+__device__ __forceinline__ void body_measure(const BodyDev &BB, const double (&x)[D], double fastd2, double &d, double (&n)[D], double (&V)[D],
+                                             int &act) {
     double xi[D], gx[D];
 #pragma unroll
     for (int a = 0; a < D; ++a) { n[a] = 0; V[a] = 0; }
-    int act; double sgn;
+    double sgn;
     d = body_sdf<D>(BB, x, act, sgn);
     if (d * d > fastd2) return;                       // :118
     const LeafDev &B = BB.leaf[act];
@@ -162,6 +164,11 @@ __device__ __forceinline__ void body_measure(const BodyDev &BB, const double (&x
             V[a] = -s;
         }
     }
+}
+template <int D>
+__device__ __forceinline__ void body_measure(const BodyDev &BB, const double (&x)[D], double fastd2, double &d, double (&n)[D], double (&V)[D]) {
+    int act;
+    body_measure<D>(BB, x, fastd2, d, n, V, act);
 }
 // Body.jl:56-61 (Float64)
 __device__ __forceinline__ double wl_kern(double d) { return 0.5 + 0.5 * cos(M_PI * d); }
