@@ -32,6 +32,8 @@ extern "C" {
 
 #define WL_ABI_VERSION 6
 
+/* Any other value is refused with WL_E_ARG by every entry point that takes a wl_dtype, and by wl_flow_create / wl_mg_create
+ * before anything is allocated. */
 typedef enum wl_dtype { WL_F32 = 0, WL_F64 = 1 } wl_dtype;
 
 enum { WL_OK = 0, WL_E_ARG = 10001, WL_E_LEVELS = 10002, WL_E_NOGPU = 10003, WL_E_STATE = 10004 };

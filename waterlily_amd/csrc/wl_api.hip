@@ -135,10 +135,10 @@ Ctx &ctx() {
     static Ctx c;
     return c;
 }
-int fail(int code, const char *what, const char *file, int line) {
+int fail(int code, const char *what, const char *file, int line, const char *who) {
     char buf[512];
     const char *hs = (code > 0 && code < 10000) ? hipGetErrorString((hipError_t)code) : "";
-    snprintf(buf, sizeof buf, "wlhip error %d at %s:%d: %s %s", code, file, line, what, hs);
+    snprintf(buf, sizeof buf, "wlhip error %d at %s:%d: %s%s%s %s", code, file, line, who ? who : "", who ? ": " : "", what, hs);
     ctx().err = buf;
     return code ? code : WL_E_ARG;
 }
@@ -855,6 +855,60 @@ template <class T, int D> static int conv_diff_phi(const G &g, T *r, const T *u,
     return Phi ? op_sigma_ghosts<T, D>(g, Phi, u, nu, permask) : 0;
 }
 
+// ------------------------------------------------------------------------------------------ argument checks
+// What several entry points ask of the same kind of argument is stated here once.  `who` is the entry point's name: the
+// message reads "<who>: <what>".  Nothing below touches the device.
+#define WL_BAD(who, what) return fail(WL_E_ARG, what, __FILE__, __LINE__, who)
+static int check_dtype(const char *who, wl_dtype t, const char *what = "unknown dtype") {
+    if (t != WL_F32 && t != WL_F64) WL_BAD(who, what);
+    return 0;
+}
+// kind m = WL_M_* with its component ipar on a D-dimensional grid (wl_metric; WL_R_METRIC + m below)
+static bool metric_kind_ok(int m, int ipar, int D) {
+    return !(m < 0 || m > WL_M_LAMBDA2 || (m >= WL_M_OMAG && D != 3) || (m == WL_M_CURL && (ipar < 0 || ipar > 2)));
+}
+// a field kind WL_R_* with its component ipar (wl_render_project; wl_downsample, which alone takes WL_R_FACE)
+static int check_kind(const char *who, int kind, int ipar, int D, bool face_ok) {
+    if (kind >= WL_R_METRIC) {
+        if (!metric_kind_ok(kind - WL_R_METRIC, ipar, D)) WL_BAD(who, "bad metric kind/component for this dimension");
+    } else if (face_ok && kind == WL_R_FACE) {
+        if (ipar < 0 || ipar >= D) WL_BAD(who, "WL_R_FACE averages component ipar of a vector field (0 <= ipar < D), not a scalar");
+    } else if (kind < WL_R_SCALAR || kind > WL_R_CENTRE || (kind != WL_R_SCALAR && (ipar < 0 || ipar >= D))) {
+        WL_BAD(who, "bad kind/component for this dimension");
+    }
+    return 0;
+}
+// The box lo, hi (given together or not at all) -> l, h: GLOBAL along z, `nd` directions parsed, l = 0, h = 1 in the others.
+// No box: 1 .. n - def_inset.  empty_ok: lo == hi passes (a box without cells), else lo < hi is required.
+static int parse_box(const char *who, const G &gg, int nd, int def_inset, bool empty_ok, const int32_t *lo, const int32_t *hi, int l[3], int h[3]) {
+    if ((lo != nullptr) != (hi != nullptr)) WL_BAD(who, "only one of lo and hi given");
+    l[0] = l[1] = l[2] = 0, h[0] = h[1] = h[2] = 1;
+    for (int d = 0; d < nd; ++d) {
+        const int n = d == 2 ? gg.nzg : gg.n[d];
+        l[d] = lo ? lo[d] : 1;
+        h[d] = hi ? hi[d] : n - def_inset;
+        if (!(0 <= l[d] && (empty_ok ? l[d] <= h[d] : l[d] < h[d]) && h[d] <= n - 1))
+            WL_BAD(who, empty_ok ? "bad box (0 <= lo <= hi <= n - 1 in every direction)" : "bad box (0 <= lo < hi <= n - 1 in every direction)");
+    }
+    return 0;
+}
+// a metric kind reads every neighbour of a cell: its box stays off the low ghost layer ...
+static int check_metric_box(const char *who, int D, const int l[3]) {
+    for (int d = 0; d < D; ++d)
+        if (l[d] < 1) WL_BAD(who, "the box of a metric kind must lie in inside()");
+    return 0;
+}
+// ... and on a z-slab the planes it is formed on need a plane of the local array on each side: every owned plane (a metric
+// kind), or the owned interior planes (interior: the loads and the integrals, which visit inside() alone)
+static int check_halo_planes(const char *who, const G &gg, bool interior) {
+    const Range R = r_inside(gg);
+    const bool some = interior ? (gg.D == 3 && R.count() > 0) : gg.dist;
+    const int klo = interior ? R.lo[2] : gg.zlo, khi = interior ? R.hi[2] : gg.zhi;
+    if (some && (klo < 1 || khi > gg.n[2] - 2))
+        WL_BAD(who, interior ? "an owned interior plane without a halo plane on each side" : "a metric kind on a z-slab needs a halo plane on each side");
+    return 0;
+}
+
 // ------------------------------------------------------------------------------------------ C ABI
 extern "C" {
 
@@ -976,10 +1030,10 @@ int wl_comm_rank(int *rank, int *nranks) {
     return 0;
 }
 int wl_halo_exchange(wl_dtype t, const wl_grid *g, void *a, int ncomp, int depth) {
+    WL_TRY(check_dtype("wl_halo_exchange", t));
     WL_TRY(check_grid(g));
     const G gg = mkG(g);
-    if (t == WL_F32) return halo_exchange<float>(gg, (float *)a, ncomp, depth);
-    return halo_exchange<double>(gg, (double *)a, ncomp, depth);
+    WL_DISPATCH_T(t, (halo_exchange<T>(gg, (T *)a, ncomp, depth)));
 }
 int wl_allreduce(double *vals, int n, int op) {
     Comm *cm = ctx().comm;
@@ -1048,13 +1102,22 @@ int wl_d2h_2d(void *dst, size_t dpitch, const void *src, size_t spitch, size_t w
     return 0;
 }
 
+// the opening of an entry point that takes (t, g): dtype and grid are checked before the device is touched for the scratch
 #define WL_GS()                                  \
+    WL_TRY(check_dtype(__func__, t));            \
     WL_TRY(check_grid(g));                       \
     int rc__ = 0;                                \
     Scratch &S = global_scratch(&rc__);          \
     (void)S;                                     \
     WL_TRY(rc__);                                \
     const G gg = mkG(g)
+#define WL_GS_OUT() if (!out) WL_BAD(__func__, "null output"); WL_GS()   // ... and that hands its result back through `out`
+// ... that takes two grids
+#define WL_GS2()                                 \
+    WL_TRY(check_dtype(__func__, t));            \
+    WL_TRY(check_grid(ga));                      \
+    WL_TRY(check_grid(gb));                      \
+    const G A = mkG(ga), B = mkG(gb)
 
 int wl_bc_vec(wl_dtype t, const wl_grid *g, void *a, const double A[3], int saveexit, int perdir_mask) {
     WL_GS();
@@ -1079,19 +1142,19 @@ int wl_exit_bc(wl_dtype t, const wl_grid *g, void *u, const void *u0, const doub
     } while (0)
 
 int wl_L2_inside(wl_dtype t, const wl_grid *g, const void *a, double *out) {
-    WL_GS();
+    WL_GS_OUT();
     WL_RED((red_L2<T, DD>(gg, (const T *)a, S)));
 }
 int wl_dot(wl_dtype t, const wl_grid *g, const void *a, const void *b, double *out) {
-    WL_GS();
+    WL_GS_OUT();
     WL_RED((red_dot<T, DD>(gg, (const T *)a, (const T *)b, S)));
 }
 int wl_sum(wl_dtype t, const wl_grid *g, const void *a, double *out) {
-    WL_GS();
+    WL_GS_OUT();
     WL_RED((red_sum<T, DD>(gg, (const T *)a, S)));
 }
 int wl_max(wl_dtype t, const wl_grid *g, const void *a, double *out) {
-    WL_GS();
+    WL_GS_OUT();
     WL_RED((red_max<T, DD>(gg, (const T *)a, S)));
 }
 
@@ -1118,7 +1181,7 @@ int wl_div(wl_dtype t, const wl_grid *g, void *z, const void *u) {
     WL_DISPATCH(t, g->D, (op_div<T, DD>(gg, (T *)z, (const T *)u)));
 }
 int wl_cfl(wl_dtype t, const wl_grid *g, void *sigma, const void *u, double nu, double *out) {
-    WL_GS();
+    WL_GS_OUT();
     WL_RED((op_cfl<T, DD>(gg, (T *)sigma, (const T *)u, nu, S.partials.get(), S.st.get())));
 }
 int wl_set_diag(wl_dtype t, const wl_grid *g, void *Dg, void *iD, const void *L) {
@@ -1126,26 +1189,21 @@ int wl_set_diag(wl_dtype t, const wl_grid *g, void *Dg, void *iD, const void *L)
     WL_DISPATCH(t, g->D, (op_set_diag<T, DD>(gg, (T *)Dg, (T *)iD, (const T *)L)));
 }
 int wl_restrictL(wl_dtype t, const wl_grid *ga, void *a, const wl_grid *gb, const void *b, int perdir_mask) {
-    WL_TRY(check_grid(ga));
-    WL_TRY(check_grid(gb));
-    const G A = mkG(ga), B = mkG(gb);
+    WL_GS2();
     WL_DISPATCH(t, ga->D, (restrictL_full<T, DD>(A, (T *)a, B, (const T *)b, perdir_mask)));
 }
 int wl_restrict(wl_dtype t, const wl_grid *ga, void *a, const wl_grid *gb, const void *b) {
-    WL_TRY(check_grid(ga));
-    WL_TRY(check_grid(gb));
-    const G A = mkG(ga), B = mkG(gb);
+    WL_GS2();
     WL_DISPATCH(t, ga->D, (op_restrict<T, DD>(A, (T *)a, B, (const T *)b)));
 }
 int wl_prolongate(wl_dtype t, const wl_grid *ga, void *a, const wl_grid *gb, const void *b) {
-    WL_TRY(check_grid(ga));
-    WL_TRY(check_grid(gb));
-    const G A = mkG(ga), B = mkG(gb);
+    WL_GS2();
     WL_DISPATCH(t, ga->D, (op_prolongate<T, DD>(A, (T *)a, B, (const T *)b)));
 }
 
 // ---- multigrid handle
 int wl_mg_create(wl_mg **out, wl_dtype t, int nlevels, const wl_level_desc *levels, int perdir_mask) {
+    WL_TRY(check_dtype("wl_mg_create", t));
     if (!out || !levels || nlevels < 1) return fail(WL_E_ARG, "wl_mg_create: bad arguments", __FILE__, __LINE__);
     if (nlevels == 2) return fail(WL_E_LEVELS, "MultiLevelPoisson requires size=a2^n, where n>2", __FILE__, __LINE__);
     for (int l = 0; l < nlevels; ++l) {
@@ -1242,6 +1300,7 @@ int wl_mg_uniform_rows(wl_mg *m, int level, long long *n_uniform, long long *n_r
     return 0;
 }
 int wl_mg_L2(wl_mg *m, int level, double *out) {
+    if (!out) return fail(WL_E_ARG, "wl_mg_L2: null output", __FILE__, __LINE__);
     WL_LEVEL_OK();
     int rc = [&]() -> int { WL_MG_DISPATCH((op_L2<T, DD>(lvl<T>(m, level), m->sc.partials.get(), m->sc.st.get()))); }();
     if (rc) return rc;
@@ -1285,6 +1344,7 @@ int wl_mg_solve(wl_mg *m, double tol, int itmx, int *n_iter) {
 
 // ---- flow handle
 int wl_flow_create(wl_flow **out, wl_dtype t, const wl_flow_desc *d) {
+    WL_TRY(check_dtype("wl_flow_create", t));
     if (!out || !d) return fail(WL_E_ARG, "wl_flow_create: bad arguments", __FILE__, __LINE__);
     WL_TRY(check_grid(&d->g));
     if (!d->u || !d->u0 || !d->f || !d->p || !d->sigma || !d->V || !d->mu0 || !d->mu1)
@@ -1385,8 +1445,7 @@ int wl_measure_rows_mesh(wl_flow *a, const wl_mesh *m, const wl_mesh_pose *pose,
     if (!(eps > 0)) return fail(WL_E_ARG, "wl_measure_rows_mesh: eps must be positive", __FILE__, __LINE__);
     PoseDev P;
     WL_TRY(mesh_pose(m, pose, 2 + eps + 1, P));
-    if (a->t == WL_F32) return mesh_rows<float>(a, m, P, eps, nband);
-    return mesh_rows<double>(a, m, P, eps, nband);
+    WL_DISPATCH_T(a->t, (mesh_rows<T>(a, m, P, eps, nband)));
 }
 int wl_measure_fill_mesh(wl_flow *a, const wl_mesh *m, const wl_mesh_pose *pose, double eps, int64_t *cand_dev) {
     if (!a) return fail(WL_E_ARG, "null handle", __FILE__, __LINE__);
@@ -1396,8 +1455,7 @@ int wl_measure_fill_mesh(wl_flow *a, const wl_mesh *m, const wl_mesh_pose *pose,
     WL_TRY(mesh_pose(m, pose, 2 + eps + 1, P));
     if (a->nband < 0) return fail(WL_E_STATE, "wl_measure_fill_mesh: call wl_measure_rows_mesh first", __FILE__, __LINE__);
     if (a->nband > 0 && !cand_dev) return fail(WL_E_ARG, "wl_measure_fill_mesh: null candidate buffer", __FILE__, __LINE__);
-    if (a->t == WL_F32) return mesh_fill<float>(a, m, P, eps, cand_dev);
-    return mesh_fill<double>(a, m, P, eps, cand_dev);
+    WL_DISPATCH_T(a->t, (mesh_fill<T>(a, m, P, eps, cand_dev)));
 }
 int wl_body_nds_mesh(const wl_grid *g, const wl_mesh *m, const wl_mesh_pose *pose, const int64_t *cand_dev, int64_t n, double *nds_dev) {
     WL_TRY(check_grid(g));
@@ -1438,7 +1496,7 @@ int wl_mom_step(wl_flow *a, wl_mg *b, double dt, const double U[3], const double
 // ---- Metrics.jl:94-100
 int wl_vforce(wl_dtype t, const wl_grid *g, const void *u, const int64_t *idx, const double *nds, int64_t nband, double nu,
               double out[3]) {
-    WL_GS();
+    WL_GS_OUT();
     return band_reduce(gg, S, nband, g->D, out, [&](int nb) {
         if (t == WL_F32) hipLaunchKernelGGL(k_vforce<float>, dim3(nb), dim3(256), 0, ctx().stream, gg, (const float *)u, idx, nds, nband, (float)nu, S.partials.get());
         else hipLaunchKernelGGL(k_vforce<double>, dim3(nb), dim3(256), 0, ctx().stream, gg, (const double *)u, idx, nds, nband, nu, S.partials.get());
@@ -1446,7 +1504,8 @@ int wl_vforce(wl_dtype t, const wl_grid *g, const void *u, const int64_t *idx, c
 }
 int wl_pmoment(wl_dtype t, const wl_grid *g, const void *p, const int64_t *idx, const double *nds, int64_t nband,
                const double x0[3], double out[3]) {
-    WL_GS();
+    if (!x0) WL_BAD("wl_pmoment", "null x0");
+    WL_GS_OUT();
     const double a = x0[0], b = x0[1], c = g->D > 2 ? x0[2] : 0.0;
     return band_reduce(gg, S, nband, g->D, out, [&](int nb) {
         if (t == WL_F32) hipLaunchKernelGGL(k_pmoment<float>, dim3(nb), dim3(256), 0, ctx().stream, gg, (const float *)p, idx, nds, nband, a, b, c, S.partials.get());
@@ -1456,18 +1515,13 @@ int wl_pmoment(wl_dtype t, const wl_grid *g, const void *p, const int64_t *idx, 
 // ---- Forces (wl_forces.h): every argument check comes before the first device call
 static int check_loads(const char *who, wl_dtype t, const wl_grid *g, const void *p, const void *u, const void *list, int64_t n,
                        const double *x0, const double *rows) {
-    const std::string w(who);
-    if (!g || !p || !u || !x0 || !rows) return fail(WL_E_ARG, (w + ": null grid, p, u, x0 or rows").c_str(), __FILE__, __LINE__);
-    if (t != WL_F32 && t != WL_F64) return fail(WL_E_ARG, (w + ": unknown dtype").c_str(), __FILE__, __LINE__);
-    if (n < 0) return fail(WL_E_ARG, (w + ": n < 0").c_str(), __FILE__, __LINE__);
-    if (n > 0 && !list) return fail(WL_E_ARG, (w + ": null cell list").c_str(), __FILE__, __LINE__);
-    if (g->D != 2 && g->D != 3) return fail(WL_E_ARG, (w + ": D must be 2 or 3").c_str(), __FILE__, __LINE__);
+    if (!g || !p || !u || !x0 || !rows) WL_BAD(who, "null grid, p, u, x0 or rows");
+    WL_TRY(check_dtype(who, t));
+    if (n < 0) WL_BAD(who, "n < 0");
+    if (n > 0 && !list) WL_BAD(who, "null cell list");
+    if (g->D != 2 && g->D != 3) WL_BAD(who, "D must be 2 or 3");
     WL_TRY(check_grid(g));
-    const G gg = mkG(g);
-    const Range R = r_inside(gg);
-    if (g->D == 3 && R.count() > 0 && (R.lo[2] < 1 || R.hi[2] > gg.n[2] - 2))
-        return fail(WL_E_ARG, (w + ": an owned interior plane without a halo plane on each side").c_str(), __FILE__, __LINE__);
-    return 0;
+    return check_halo_planes(who, mkG(g), true);
 }
 int wl_body_loads(wl_dtype t, const wl_grid *g, const void *p, const void *u, double nu, const wl_body_desc *body, const int64_t *cand_dev,
                   int64_t n, const double x0[3], double *rows_dev) {
@@ -1475,14 +1529,8 @@ int wl_body_loads(wl_dtype t, const wl_grid *g, const void *p, const void *u, do
     WL_TRY(check_body(body, g->D));
     WL_GS();
     const int nleaf = body[0].count > 0 ? body[0].count : 1;
-    if (g->D == 3) {
-        const LoadsBody<3> src{body_dev(body), (const long *)cand_dev};
-        if (t == WL_F32) return op_loads<float, 3>(gg, src, (const float *)p, (const float *)u, nu, (long)n, x0, nleaf, S.partials.get(), rows_dev);
-        return op_loads<double, 3>(gg, src, (const double *)p, (const double *)u, nu, (long)n, x0, nleaf, S.partials.get(), rows_dev);
-    }
-    const LoadsBody<2> src{body_dev(body), (const long *)cand_dev};
-    if (t == WL_F32) return op_loads<float, 2>(gg, src, (const float *)p, (const float *)u, nu, (long)n, x0, nleaf, S.partials.get(), rows_dev);
-    return op_loads<double, 2>(gg, src, (const double *)p, (const double *)u, nu, (long)n, x0, nleaf, S.partials.get(), rows_dev);
+    WL_DISPATCH(t, g->D, (op_loads<T, DD>(gg, LoadsBody<DD>{body_dev(body), (const long *)cand_dev}, (const T *)p, (const T *)u, nu, (long)n, x0, nleaf,
+                                          S.partials.get(), rows_dev)));
 }
 int wl_body_loads_mesh(wl_dtype t, const wl_grid *g, const void *p, const void *u, double nu, const wl_mesh *m, const wl_mesh_pose *pose,
                        const int64_t *cand_dev, int64_t n, const double x0[3], double *rows_dev) {
@@ -1494,33 +1542,27 @@ int wl_body_loads_mesh(wl_dtype t, const wl_grid *g, const void *p, const void *
     WL_TRY(mesh_upload(m));
     src.M = m->view(true);
     src.cand = (const long *)cand_dev;
-    if (t == WL_F32) return op_loads<float, 3>(gg, src, (const float *)p, (const float *)u, nu, (long)n, x0, 1, S.partials.get(), rows_dev);
-    return op_loads<double, 3>(gg, src, (const double *)p, (const double *)u, nu, (long)n, x0, 1, S.partials.get(), rows_dev);
+    WL_DISPATCH_T(t, (op_loads<T, 3>(gg, src, (const T *)p, (const T *)u, nu, (long)n, x0, 1, S.partials.get(), rows_dev)));
 }
 int wl_band_loads(wl_dtype t, const wl_grid *g, const void *p, const void *u, double nu, const int64_t *idx_dev, const double *nds_dev,
                   int64_t n, const double x0[3], double *rows_dev) {
     WL_TRY(check_loads("wl_band_loads", t, g, p, u, idx_dev, n, x0, rows_dev));
     if (n > 0 && !nds_dev) return fail(WL_E_ARG, "wl_band_loads: null nds", __FILE__, __LINE__);
     WL_GS();
-    if (g->D == 3) {
-        const LoadsBand<3> src{idx_dev, nds_dev};
-        if (t == WL_F32) return op_loads<float, 3>(gg, src, (const float *)p, (const float *)u, nu, (long)n, x0, 1, S.partials.get(), rows_dev);
-        return op_loads<double, 3>(gg, src, (const double *)p, (const double *)u, nu, (long)n, x0, 1, S.partials.get(), rows_dev);
-    }
-    const LoadsBand<2> src{idx_dev, nds_dev};
-    if (t == WL_F32) return op_loads<float, 2>(gg, src, (const float *)p, (const float *)u, nu, (long)n, x0, 1, S.partials.get(), rows_dev);
-    return op_loads<double, 2>(gg, src, (const double *)p, (const double *)u, nu, (long)n, x0, 1, S.partials.get(), rows_dev);
+    WL_DISPATCH(t, g->D, (op_loads<T, DD>(gg, LoadsBand<DD>{idx_dev, nds_dev}, (const T *)p, (const T *)u, nu, (long)n, x0, 1, S.partials.get(), rows_dev)));
 }
 int wl_metric(wl_dtype t, const wl_grid *g, int kind, void *out, const void *u, int ipar, const double par[3],
               const double par2[3]) {
     WL_GS();
-    if (kind < 0 || kind > WL_M_LAMBDA2 || (kind >= WL_M_OMAG && g->D != 3) || (kind == WL_M_CURL && (ipar < 0 || ipar > 2)))
+    if (!metric_kind_ok(kind, ipar, g->D))
         return fail(WL_E_ARG, "wl_metric: bad kind/component for this dimension", __FILE__, __LINE__);
     WL_DISPATCH(t, g->D, (op_metric<T, DD>(gg, kind, (T *)out, (const T *)u, ipar, par, par2)));
 }
 int wl_flow_integrals(wl_dtype t, const wl_grid *g, const void *u, const double U[3], double *row_dev) {
     if (!g || !u || !U || !row_dev) return fail(WL_E_ARG, "wl_flow_integrals: null grid, u, U or row", __FILE__, __LINE__);
     if (g->D != 2 && g->D != 3) return fail(WL_E_ARG, "wl_flow_integrals: D must be 2 or 3", __FILE__, __LINE__);
+    WL_TRY(check_grid(g));
+    WL_TRY(check_halo_planes("wl_flow_integrals", mkG(g), true));
     WL_GS();
     WL_DISPATCH(t, g->D, (op_integrals<T, DD>(gg, (const T *)u, U, S.partials.get(), row_dev)));
 }
@@ -1528,8 +1570,8 @@ int wl_meanflow_update(wl_dtype t_flow, wl_dtype t_acc, const wl_grid *g, const 
                        void *P, void *UU, void *pp, double eps, int first) {
     WL_TRY(check_grid(g));
     WL_TRY(check_grid(ga));
-    if ((t_flow != WL_F32 && t_flow != WL_F64) || (t_acc != WL_F32 && t_acc != WL_F64))
-        return fail(WL_E_ARG, "wl_meanflow_update: unknown dtype", __FILE__, __LINE__);
+    WL_TRY(check_dtype("wl_meanflow_update", t_flow));
+    WL_TRY(check_dtype("wl_meanflow_update", t_acc));
     if (t_flow == WL_F64 && t_acc == WL_F32)
         return fail(WL_E_ARG, "wl_meanflow_update: Float32 accumulators on a Float64 flow", __FILE__, __LINE__);
     if (!u || !p || !U || !P) return fail(WL_E_ARG, "wl_meanflow_update: null u, p, U or P", __FILE__, __LINE__);
@@ -1540,21 +1582,17 @@ int wl_meanflow_update(wl_dtype t_flow, wl_dtype t_acc, const wl_grid *g, const 
     if (!same) return fail(WL_E_ARG, "wl_meanflow_update: the accumulators' grid must have the flow grid's extents and slab", __FILE__, __LINE__);
     if (!(eps > 0.0 && eps <= 1.0)) return fail(WL_E_ARG, "wl_meanflow_update: eps must lie in (0, 1]", __FILE__, __LINE__);
     const G gf = mkG(g), gacc = mkG(ga);
-    if (t_flow == WL_F32 && t_acc == WL_F32) {
-        if (g->D == 2) return op_meanflow<float, float, 2>(gf, gacc, (const float *)u, (const float *)p, (float *)U, (float *)P, (float *)UU, (float *)pp, eps, first);
-        return op_meanflow<float, float, 3>(gf, gacc, (const float *)u, (const float *)p, (float *)U, (float *)P, (float *)UU, (float *)pp, eps, first);
-    }
-    if (t_flow == WL_F32) {
-        if (g->D == 2) return op_meanflow<float, double, 2>(gf, gacc, (const float *)u, (const float *)p, (double *)U, (double *)P, (double *)UU, (double *)pp, eps, first);
-        return op_meanflow<float, double, 3>(gf, gacc, (const float *)u, (const float *)p, (double *)U, (double *)P, (double *)UU, (double *)pp, eps, first);
-    }
-    if (g->D == 2) return op_meanflow<double, double, 2>(gf, gacc, (const double *)u, (const double *)p, (double *)U, (double *)P, (double *)UU, (double *)pp, eps, first);
-    return op_meanflow<double, double, 3>(gf, gacc, (const double *)u, (const double *)p, (double *)U, (double *)P, (double *)UU, (double *)pp, eps, first);
+    // the three (flow, accumulator) pairs: Float64 accumulators on either flow, Float32 ones on a Float32 flow (checked above)
+#define WL_MEANFLOW(TF, TA, DD) op_meanflow<TF, TA, DD>(gf, gacc, (const TF *)u, (const TF *)p, (TA *)U, (TA *)P, (TA *)UU, (TA *)pp, eps, first)
+    if (t_acc == WL_F64) WL_DISPATCH(t_flow, g->D, (WL_MEANFLOW(T, double, DD)));
+    if (g->D == 3) return WL_MEANFLOW(float, float, 3);
+    return WL_MEANFLOW(float, float, 2);
+#undef WL_MEANFLOW
 }
 int wl_interp(wl_dtype t, const wl_grid *g, const void *a, int ncomp, const double *x_dev, int64_t m, double *out_dev,
               int64_t ldo) {
     WL_TRY(check_grid(g));
-    if (t != WL_F32 && t != WL_F64) return fail(WL_E_ARG, "wl_interp: unknown dtype", __FILE__, __LINE__);
+    WL_TRY(check_dtype("wl_interp", t));
     if (!a || !x_dev || !out_dev) return fail(WL_E_ARG, "wl_interp: null field, points or output", __FILE__, __LINE__);
     if (ncomp != 0 && ncomp != g->D) return fail(WL_E_ARG, "wl_interp: ncomp must be 0 (scalar) or D (staggered vector)", __FILE__, __LINE__);
     if (m < 0) return fail(WL_E_ARG, "wl_interp: negative number of points", __FILE__, __LINE__);
@@ -1568,7 +1606,7 @@ int wl_surface_sample(wl_dtype t, const wl_grid *g, const void *p, const void *u
     if (!rows_dev) return fail(WL_E_ARG, "wl_surface_sample: null output rows", __FILE__, __LINE__);
     WL_TRY(check_grid(g));
     if (g->D != 3) return fail(WL_E_ARG, "wl_surface_sample: a triangle mesh needs D == 3", __FILE__, __LINE__);
-    if (t != WL_F32 && t != WL_F64) return fail(WL_E_ARG, "wl_surface_sample: unknown dtype", __FILE__, __LINE__);
+    WL_TRY(check_dtype("wl_surface_sample", t));
     if (!p || !u) return fail(WL_E_ARG, "wl_surface_sample: null p or u", __FILE__, __LINE__);
     if (!(std::isfinite(delta) && delta >= 0.0)) return fail(WL_E_ARG, "wl_surface_sample: delta must be finite and >= 0", __FILE__, __LINE__);
     if (!std::isfinite(nu)) return fail(WL_E_ARG, "wl_surface_sample: nu must be finite", __FILE__, __LINE__);
@@ -1578,9 +1616,7 @@ int wl_surface_sample(wl_dtype t, const wl_grid *g, const void *p, const void *u
     WL_TRY(mesh_upload(m));
     const G gg = mkG(g);
     const MeshDev M = m->view(true);
-    if (t == WL_F32)
-        return op_surface_sample<float>(gg, M, m->nt, P, (const float *)p, (const float *)u, delta, nu, rows_dev, geom_dev, mean_dev, w, first);
-    return op_surface_sample<double>(gg, M, m->nt, P, (const double *)p, (const double *)u, delta, nu, rows_dev, geom_dev, mean_dev, w, first);
+    WL_DISPATCH_T(t, (op_surface_sample<T>(gg, M, m->nt, P, (const T *)p, (const T *)u, delta, nu, rows_dev, geom_dev, mean_dev, w, first)));
 }
 int wl_surface_totals(const double *rows_dev, const double *geom_dev, int64_t nt, const double x0[3], double *out_dev) {
     if (!rows_dev || !geom_dev || !x0 || !out_dev) return fail(WL_E_ARG, "wl_surface_totals: null rows, geometry, x0 or output", __FILE__, __LINE__);
@@ -1605,54 +1641,32 @@ int wl_isosurface(wl_dtype t, const wl_grid *g, const void *a, const void *b, do
     if (!g || !a || !count_dev) return fail(WL_E_ARG, "wl_isosurface: null grid, field or count", __FILE__, __LINE__);
     WL_TRY(check_grid(g));
     if (g->D != 3) return fail(WL_E_ARG, "wl_isosurface: an isosurface needs D == 3", __FILE__, __LINE__);
-    if (t != WL_F32 && t != WL_F64) return fail(WL_E_ARG, "wl_isosurface: unknown dtype", __FILE__, __LINE__);
+    WL_TRY(check_dtype("wl_isosurface", t));
     if (!std::isfinite(c)) return fail(WL_E_ARG, "wl_isosurface: the level c must be finite", __FILE__, __LINE__);
     if (cap < 0) return fail(WL_E_ARG, "wl_isosurface: negative capacity", __FILE__, __LINE__);
     if (cap > 0 && !tri_dev) return fail(WL_E_ARG, "wl_isosurface: null triangle buffer with cap > 0", __FILE__, __LINE__);
     if ((b != nullptr) != (val_dev != nullptr))
         return fail(WL_E_ARG, "wl_isosurface: the colour field b and val_dev must be given together", __FILE__, __LINE__);
-    if ((lo != nullptr) != (hi != nullptr)) return fail(WL_E_ARG, "wl_isosurface: only one of lo and hi given", __FILE__, __LINE__);
     const G gg = mkG(g);
     int l[3], h[3];
-    for (int d = 0; d < 3; ++d) {
-        const int n = d == 2 ? gg.nzg : gg.n[d];
-        l[d] = lo ? lo[d] : 1;
-        h[d] = hi ? hi[d] : n - 2;
-        if (!(0 <= l[d] && l[d] <= h[d] && h[d] <= n - 1))
-            return fail(WL_E_ARG, "wl_isosurface: bad box (0 <= lo <= hi <= n - 1 in every direction)", __FILE__, __LINE__);
-    }
-    if (t == WL_F32) return op_isosurface<float>(gg, (const float *)a, (const float *)b, c, l, h, tri_dev, val_dev, cap, count_dev);
-    return op_isosurface<double>(gg, (const double *)a, (const double *)b, c, l, h, tri_dev, val_dev, cap, count_dev);
+    WL_TRY(parse_box("wl_isosurface", gg, 3, 2, true, lo, hi, l, h));   // (no box: the cells whose upper corner is in inside())
+    WL_DISPATCH_T(t, (op_isosurface<T>(gg, (const T *)a, (const T *)b, c, l, h, tri_dev, val_dev, cap, count_dev)));
 }
 int wl_render_project(wl_dtype t, const wl_grid *g, const void *f, int kind, int ipar, const double par[3], const double par2[3],
                       int axis, int mode, const int32_t lo[3], const int32_t hi[3], double *img_dev, int64_t ld) {
     if (!g || !f || !img_dev) return fail(WL_E_ARG, "wl_render_project: null grid, field or image", __FILE__, __LINE__);
     WL_TRY(check_grid(g));
-    if (t != WL_F32 && t != WL_F64) return fail(WL_E_ARG, "wl_render_project: unknown dtype", __FILE__, __LINE__);
+    WL_TRY(check_dtype("wl_render_project", t));
     const int D = g->D;
     const bool metric = kind >= WL_R_METRIC;
-    if (metric) {
-        const int m = kind - WL_R_METRIC;
-        if (m > WL_M_LAMBDA2 || (m >= WL_M_OMAG && D != 3) || (m == WL_M_CURL && (ipar < 0 || ipar > 2)))
-            return fail(WL_E_ARG, "wl_render_project: bad metric kind/component for this dimension", __FILE__, __LINE__);
-    } else if (kind < WL_R_SCALAR || kind > WL_R_CENTRE || (kind != WL_R_SCALAR && (ipar < 0 || ipar >= D))) {
-        return fail(WL_E_ARG, "wl_render_project: bad kind/component for this dimension", __FILE__, __LINE__);
-    }
+    WL_TRY(check_kind("wl_render_project", kind, ipar, D, false));
     if (mode < WL_R_MAX || mode > WL_R_MEAN) return fail(WL_E_ARG, "wl_render_project: bad mode", __FILE__, __LINE__);
     if (D == 2 ? axis != 2 : (axis < 0 || axis > 2)) return fail(WL_E_ARG, "wl_render_project: bad axis (0..2; a 2-D grid takes 2)", __FILE__, __LINE__);
-    if ((lo != nullptr) != (hi != nullptr)) return fail(WL_E_ARG, "wl_render_project: only one of lo and hi given", __FILE__, __LINE__);
     const G gg = mkG(g);
-    int l[3] = {0, 0, 0}, h[3] = {1, 1, 1};
-    for (int d = 0; d < D; ++d) {
-        const int n = d == 2 ? gg.nzg : gg.n[d];
-        l[d] = lo ? lo[d] : 1;
-        h[d] = hi ? hi[d] : n - 1;
-        if (!(0 <= l[d] && l[d] <= h[d] && h[d] <= n - 1))
-            return fail(WL_E_ARG, "wl_render_project: bad box (0 <= lo <= hi <= n - 1 in every direction)", __FILE__, __LINE__);
-        if (metric && l[d] < 1) return fail(WL_E_ARG, "wl_render_project: the box of a metric kind must lie in inside()", __FILE__, __LINE__);
-    }
-    if (metric && gg.dist && (gg.zlo < 1 || gg.zhi > gg.n[2] - 2))
-        return fail(WL_E_ARG, "wl_render_project: a metric kind on a z-slab needs a halo plane on each side", __FILE__, __LINE__);
+    int l[3], h[3];
+    WL_TRY(parse_box("wl_render_project", gg, D, 1, true, lo, hi, l, h));
+    if (metric) WL_TRY(check_metric_box("wl_render_project", D, l));
+    if (metric) WL_TRY(check_halo_planes("wl_render_project", gg, false));
     const int wa = axis == 0 ? 1 : 0;
     if (ld < (int64_t)(h[wa] - l[wa])) return fail(WL_E_ARG, "wl_render_project: ld smaller than the image width", __FILE__, __LINE__);
     WL_DISPATCH(t, D, (op_render_project<T, DD>(gg, (const T *)f, kind, ipar, par, par2, axis, mode, l, h, img_dev, ld)));
@@ -1674,21 +1688,12 @@ int wl_render_shade(const double *img_dev, int64_t ld, int nx, int ny, double vm
     A.vmin = vmin; A.vmax = vmax; A.mask_lt = mask_lt; A.mask_rgba = mask_dev ? word(mask_rgba) : 0u; A.nan_rgba = word(nan_rgba);
     return op_render_shade(A, img_dev, mask_dev, lut_dev, rgba_dev);
 }
-// the checks wl_downsample and wl_downsample_extent share: factor and box -> l, h (GLOBAL; D == 2: l[2] = 0, h[2] = 1)
+// the checks wl_downsample and wl_downsample_extent share: factor and box -> l, h (a box without cells is refused here)
 static int downsample_box(const char *who, const wl_grid *g, const G &gg, int factor, const int32_t lo[3], const int32_t hi[3], int l[3], int h[3]) {
-    char msg[160];
-    auto bad = [&](const char *what) { snprintf(msg, sizeof msg, "%s: %s", who, what); return fail(WL_E_ARG, msg, __FILE__, __LINE__); };
-    if (factor != 1 && factor != 2 && factor != 4 && factor != 8 && factor != 16) return bad("bad factor (1, 2, 4, 8 or 16)");
-    if ((lo != nullptr) != (hi != nullptr)) return bad("only one of lo and hi given");
-    l[0] = l[1] = l[2] = 0;
-    h[0] = h[1] = h[2] = 1;
-    for (int d = 0; d < g->D; ++d) {
-        const int n = d == 2 ? gg.nzg : gg.n[d];
-        l[d] = lo ? lo[d] : 1;
-        h[d] = hi ? hi[d] : n - 1;
-        if (!(0 <= l[d] && l[d] < h[d] && h[d] <= n - 1)) return bad("bad box (0 <= lo < hi <= n - 1 in every direction)");
-        if ((h[d] - l[d]) % factor != 0) return bad("the extents hi - lo of the box must be multiples of factor");
-    }
+    if (factor != 1 && factor != 2 && factor != 4 && factor != 8 && factor != 16) WL_BAD(who, "bad factor (1, 2, 4, 8 or 16)");
+    WL_TRY(parse_box(who, gg, g->D, 1, false, lo, hi, l, h));
+    for (int d = 0; d < g->D; ++d)
+        if ((h[d] - l[d]) % factor != 0) WL_BAD(who, "the extents hi - lo of the box must be multiples of factor");
     return 0;
 }
 int wl_downsample_extent(const wl_grid *g, int factor, const int32_t lo[3], const int32_t hi[3], int32_t nc[3], int32_t *k0) {
@@ -1707,31 +1712,19 @@ int wl_downsample(wl_dtype t, const wl_grid *g, const void *f, int kind, int ipa
                   int factor, const int32_t lo[3], const int32_t hi[3], wl_dtype t_out, void *out_dev, int ntuple, int c) {
     if (!g || !f || !out_dev) return fail(WL_E_ARG, "wl_downsample: null grid, field or output", __FILE__, __LINE__);
     WL_TRY(check_grid(g));
-    if (t != WL_F32 && t != WL_F64) return fail(WL_E_ARG, "wl_downsample: unknown dtype t", __FILE__, __LINE__);
-    if (t_out != WL_F32 && t_out != WL_F64) return fail(WL_E_ARG, "wl_downsample: unknown dtype t_out", __FILE__, __LINE__);
+    WL_TRY(check_dtype("wl_downsample", t, "unknown dtype t"));
+    WL_TRY(check_dtype("wl_downsample", t_out, "unknown dtype t_out"));
     const int D = g->D;
     const bool metric = kind >= WL_R_METRIC;
-    if (metric) {
-        const int m = kind - WL_R_METRIC;
-        if (m > WL_M_LAMBDA2 || (m >= WL_M_OMAG && D != 3) || (m == WL_M_CURL && (ipar < 0 || ipar > 2)))
-            return fail(WL_E_ARG, "wl_downsample: bad metric kind/component for this dimension", __FILE__, __LINE__);
-    } else if (kind == WL_R_FACE) {
-        if (ipar < 0 || ipar >= D)
-            return fail(WL_E_ARG, "wl_downsample: WL_R_FACE averages component ipar of a vector field (0 <= ipar < D), not a scalar", __FILE__, __LINE__);
-    } else if (kind < WL_R_SCALAR || kind > WL_R_CENTRE || (kind != WL_R_SCALAR && (ipar < 0 || ipar >= D))) {
-        return fail(WL_E_ARG, "wl_downsample: bad kind/component for this dimension", __FILE__, __LINE__);
-    }
+    WL_TRY(check_kind("wl_downsample", kind, ipar, D, true));
     if (mode < WL_R_MAX || mode > WL_R_SAMPLE) return fail(WL_E_ARG, "wl_downsample: bad mode", __FILE__, __LINE__);
     if (ntuple < 1 || ntuple > 9) return fail(WL_E_ARG, "wl_downsample: bad ntuple (1 <= ntuple <= 9)", __FILE__, __LINE__);
     if (c < 0 || c >= ntuple) return fail(WL_E_ARG, "wl_downsample: bad c (0 <= c < ntuple)", __FILE__, __LINE__);
     const G gg = mkG(g);
     int l[3], h[3], nc[3], k0, klo;
     WL_TRY(downsample_box("wl_downsample", g, gg, factor, lo, hi, l, h));
-    if (metric)
-        for (int d = 0; d < D; ++d)
-            if (l[d] < 1) return fail(WL_E_ARG, "wl_downsample: the box of a metric kind must lie in inside()", __FILE__, __LINE__);
-    if (metric && gg.dist && (gg.zlo < 1 || gg.zhi > gg.n[2] - 2))
-        return fail(WL_E_ARG, "wl_downsample: a metric kind on a z-slab needs a halo plane on each side", __FILE__, __LINE__);
+    if (metric) WL_TRY(check_metric_box("wl_downsample", D, l));
+    if (metric) WL_TRY(check_halo_planes("wl_downsample", gg, false));
     if (!down_extent(gg, factor, l, h, nc, &k0, &klo))
         return fail(WL_E_ARG, "wl_downsample: a boundary of this rank's planes inside the box is not at lo_2 + m*factor", __FILE__, __LINE__);
     l[2] = klo;
@@ -1739,7 +1732,7 @@ int wl_downsample(wl_dtype t, const wl_grid *g, const void *f, int kind, int ipa
 }
 int wl_tracer_advance(wl_dtype t, const wl_grid *g, const void *u, double *x_dev, int64_t m, double dt, int perdir_mask) {
     WL_TRY(check_grid(g));
-    if (t != WL_F32 && t != WL_F64) return fail(WL_E_ARG, "wl_tracer_advance: unknown dtype", __FILE__, __LINE__);
+    WL_TRY(check_dtype("wl_tracer_advance", t));
     if (!u || !x_dev) return fail(WL_E_ARG, "wl_tracer_advance: null velocity or positions", __FILE__, __LINE__);
     if (m < 0) return fail(WL_E_ARG, "wl_tracer_advance: negative number of particles", __FILE__, __LINE__);
     if (!(std::isfinite(dt) && dt >= 0.0)) return fail(WL_E_ARG, "wl_tracer_advance: dt must be finite and >= 0", __FILE__, __LINE__);
@@ -1751,7 +1744,7 @@ int wl_tracer_advance(wl_dtype t, const wl_grid *g, const void *u, double *x_dev
 }
 int wl_pforce(wl_dtype t, const wl_grid *g, const void *p, const int64_t *idx, const double *nds, int64_t nband,
               double out[3]) {
-    WL_GS();
+    WL_GS_OUT();
     (void)gg;
     out[0] = out[1] = out[2] = 0;
     int nb = (int)((nband + 255) / 256);
@@ -1759,10 +1752,8 @@ int wl_pforce(wl_dtype t, const wl_grid *g, const void *p, const int64_t *idx, c
     if (nband <= 0) nb = 0;   // a rank whose slab holds no part of the body still joins the all-reduce
     if (nb > 0) {
         Prof pr(WL_K_PFORCE, nband);
-        if (t == WL_F32)
-            hipLaunchKernelGGL(k_pforce<float>, dim3(nb), dim3(256), 0, ctx().stream, (const float *)p, idx, nds, nband, g->D, S.partials.get());
-        else
-            hipLaunchKernelGGL(k_pforce<double>, dim3(nb), dim3(256), 0, ctx().stream, (const double *)p, idx, nds, nband, g->D, S.partials.get());
+        if (t == WL_F32) hipLaunchKernelGGL(k_pforce<float>, dim3(nb), dim3(256), 0, ctx().stream, (const float *)p, idx, nds, nband, g->D, S.partials.get());
+        else hipLaunchKernelGGL(k_pforce<double>, dim3(nb), dim3(256), 0, ctx().stream, (const double *)p, idx, nds, nband, g->D, S.partials.get());
         WL_HIP(hipGetLastError());
     }
     State *st = S.st.get();
@@ -1782,16 +1773,16 @@ static int snapshot_args(const wl_grid *g, const void *a, int ncomp, int nct, in
     return 0;
 }
 int wl_snapshot_pack(wl_dtype t, const wl_grid *g, const void *a, int ncomp, int ntuple, int klo, int khi, void *dst) {
+    WL_TRY(check_dtype("wl_snapshot_pack", t));
     WL_TRY(snapshot_args(g, a, ncomp, ntuple, klo, khi, dst));
     const G gg = mkG(g);
-    if (t == WL_F32) return snapshot_copy<float>(gg, (float *)const_cast<void *>(a), ncomp, ntuple, klo, khi, (float *)dst, true);
-    return snapshot_copy<double>(gg, (double *)const_cast<void *>(a), ncomp, ntuple, klo, khi, (double *)dst, true);
+    WL_DISPATCH_T(t, (snapshot_copy<T>(gg, (T *)const_cast<void *>(a), ncomp, ntuple, klo, khi, (T *)dst, true)));
 }
 int wl_snapshot_unpack(wl_dtype t, const wl_grid *g, void *a, int ncomp, int ntuple, int klo, int khi, const void *src) {
+    WL_TRY(check_dtype("wl_snapshot_unpack", t));
     WL_TRY(snapshot_args(g, a, ncomp, ntuple, klo, khi, src));
     const G gg = mkG(g);
-    if (t == WL_F32) return snapshot_copy<float>(gg, (float *)a, ncomp, ntuple, klo, khi, (float *)const_cast<void *>(src), false);
-    return snapshot_copy<double>(gg, (double *)a, ncomp, ntuple, klo, khi, (double *)const_cast<void *>(src), false);
+    WL_DISPATCH_T(t, (snapshot_copy<T>(gg, (T *)a, ncomp, ntuple, klo, khi, (T *)const_cast<void *>(src), false)));
 }
 
 int wl_set_option(int key, int value) {

@@ -119,7 +119,8 @@ inline int opt(int key) { return ctx().opt.v[key]; }   // current value of WL_OP
 // every allocation of the library goes through these two (counted: a steady time step must not allocate, test/alloctest.jl)
 inline hipError_t wl_dev_alloc(void **p, size_t n) { ctx().n_alloc += 1; ctx().alloc_bytes += (int64_t)n; return hipMalloc(p, n); }
 inline hipError_t wl_host_alloc(void **p, size_t n, unsigned flags) { ctx().n_alloc += 1; ctx().alloc_bytes += (int64_t)n; return hipHostMalloc(p, n, flags); }
-int fail(int code, const char *what, const char *file, int line);
+// records "<who>: <what>" (or `what` alone) as wl_last_error() and returns the code: the one place a message is put together
+int fail(int code, const char *what, const char *file, int line, const char *who = nullptr);
 // ... as the policies of Buf (wl_buf.h), which owns every block the library allocates; a failure is reported here
 struct DevMem {
     static int alloc(void **p, size_t bytes) {
@@ -833,6 +834,13 @@ _Pragma("unroll")
         if ((t) == WL_F64 && (D) == 3) { using T = double; constexpr int DD = 3; return CALL; }  \
         if ((t) == WL_F64 && (D) == 2) { using T = double; constexpr int DD = 2; return CALL; }  \
         return ::wl::fail(WL_E_ARG, "unsupported dtype/dimension", __FILE__, __LINE__);          \
+    } while (0)
+// ... on the dtype alone (calls that exist for D == 3 only, or that take D at run time)
+#define WL_DISPATCH_T(t, CALL)                                           \
+    do {                                                                 \
+        if ((t) == WL_F32) { using T = float; return CALL; }             \
+        if ((t) == WL_F64) { using T = double; return CALL; }            \
+        return ::wl::fail(WL_E_ARG, "unsupported dtype", __FILE__, __LINE__);                    \
     } while (0)
 
 }  // namespace wl

@@ -226,15 +226,13 @@ __global__ __launch_bounds__(WL_FIN_T) void k_integrals_fin(const double *__rest
 }
 
 // two launches, nothing allocated, nothing communicated: a z-slab rank writes the row of its own planes (all zeros when it
-// owns no interior plane)
+// owns no interior plane).  That those planes have a halo plane on each side is the caller's check (wl_flow_integrals).
 template <class T, int D>
 int op_integrals(const G &g, const T *u, const double *U, double *partials, double *row) {
     constexpr int NV = 6 + D;
     const Range R = r_inside(g);
     int np = 0;
     if (R.count() > 0) {
-        if (D == 3 && (R.lo[2] < 1 || R.hi[2] > g.n[2] - 2))
-            return fail(WL_E_ARG, "wl_flow_integrals: an owned interior plane without a halo plane on each side", __FILE__, __LINE__);
         const Tiling t = ig_tiling(R);
         np = t.nblk;
         if ((long)NV * np > 4L * WL_MAXB) return fail(WL_E_ARG, "wl_flow_integrals: grid too large for the reduction scratch", __FILE__, __LINE__);

@@ -61,14 +61,10 @@ class _DevBuf:
             self.ptr = None
 
 
-def _i3(v):
-    return (C.c_int32 * 3)(*([int(x) for x in v] + [0] * 3)[:3])
-
-
 def extent(g, factor: int, lo, hi) -> Tuple[Tuple[int, int, int], int]:
     """wl_downsample_extent: (this rank's coarse extents (ncx, ncy, ncz), its first coarse plane) for the grid g and the box"""
     nc, k0 = (C.c_int32 * 3)(), C.c_int32()
-    check(_lib.lib().wl_downsample_extent(C.byref(g), int(factor), _i3(lo), _i3(hi), nc, C.byref(k0)))
+    check(_lib.lib().wl_downsample_extent(C.byref(g), int(factor), render._i3(lo), render._i3(hi), nc, C.byref(k0)))
     return (int(nc[0]), int(nc[1]), int(nc[2])), int(k0.value)
 
 
@@ -111,22 +107,11 @@ class Downsampler:
         self._vel: Optional[_DevBuf] = None
 
 
-def _field_grid(d: Downsampler, f: torch.Tensor, vector: bool):
-    ref = d.flow.u if vector else d.flow.p
-    if tuple(f.shape) != tuple(ref.shape) or f.stride() != ref.stride() or f.dtype != ref.dtype:
-        raise ValueError(f"Downsampler: the field must have the layout of flow.{'u' if vector else 'p'} (use waterlily_amd.sim.like)")
-    return S._grid_of(f, d.D)
-
-
 def _call(d: Downsampler, f: torch.Tensor, k: int, m: int, i: int, par, par2, box, ptr: int, ntuple: int, c: int) -> None:
-    g = _field_grid(d, f, vector=(k != render.R_SCALAR))
+    g = render._field_grid(d.flow, f, k != render.R_SCALAR, "Downsampler")
     check(_lib.lib().wl_downsample(S._WLT[S._T(f)], C.byref(g), S._ptr(f), k, int(i), None if par is None else _lib.d3(par),
-                                   None if par2 is None else _lib.d3(par2), m, d.factor, _i3(box[0]), _i3(box[1]), S._WLT[d.T],
+                                   None if par2 is None else _lib.d3(par2), m, d.factor, render._i3(box[0]), render._i3(box[1]), S._WLT[d.T],
                                    C.c_void_p(ptr), int(ntuple), int(c)))
-
-
-def _codes(kind, mode):
-    return (_KIND[kind] if isinstance(kind, str) else int(kind)), (_MODE[mode] if isinstance(mode, str) else int(mode))
 
 
 def volume(d: Downsampler, f: torch.Tensor, kind="scalar", mode: str = "mean", i: int = 0, par=None, par2=None) -> torch.Tensor:
@@ -135,8 +120,7 @@ def volume(d: Downsampler, f: torch.Tensor, kind="scalar", mode: str = "mean", i
     cell centre / the fine faces on the block's low i-face), or a metric of f = u: "ke", "curl", "omega_mag", "omega_theta",
     "lambda2" (i, par, par2 as waterlily_amd.sim.metric).  mode: "mean", "sum", "max", "min", "absmax" (the signed value of
     largest magnitude), "sample" (the block's first cell).  On a z-slab the view holds this rank's coarse planes."""
-    k, m = _codes(kind, mode)
-    _call(d, f, k, m, i, par, par2, d.box, d._vol.ptr, 1, 0)
+    _call(d, f, render._code(_KIND, kind), render._code(_MODE, mode), i, par, par2, d.box, d._vol.ptr, 1, 0)
     nc = d.nc
     t = d._vol.tensor(S._TORCH[d.T], d.flow.device)[:nc[0] * nc[1] * nc[2]]
     return t.view(nc[1], nc[0]).permute(1, 0) if d.D == 2 else t.view(nc[2], nc[1], nc[0]).permute(2, 1, 0)
@@ -228,7 +212,7 @@ def _plan(w: DownsampleWriter, sim):
         a = func(sim)
         if not isinstance(a, torch.Tensor) or not a.is_cuda:
             raise TypeError(f"attribute {name!r}: the function must return a device field of the simulation (e.g. sim.flow.u)")
-        k, m = _codes(kind, mode)
+        k, m = render._code(_KIND, kind), render._code(_MODE, mode)
         vec = a.ndim > D and k in (render.R_UCOMP, render.R_CENTRE, R_FACE)
         nct = 3 if vec else 1                                   # vectors carry 3 components (2-D: a zero third one)
         n = nc[0] * nc[1] * nc[2] * nct * tsz

@@ -30,17 +30,18 @@ ranks' rows at the host, in rank order (every column is additive; NaN stays NaN)
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, List, Sequence, Tuple
+from typing import Dict, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from . import _lib
+from . import _series
 from . import body as B
 from . import sim as S
 from ._lib import check
 from .mesh import MeshBody
-from .probes import _rank_parts
+from ._series import _rank_parts
 
 NV = 16
 _COLUMNS = ("Fp_x", "Fp_y", "Fp_z", "Fv_x", "Fv_y", "Fv_z", "Mp_x", "Mp_y", "Mp_z", "Mv_x", "Mv_y", "Mv_z", "Wp", "Wv", "ncells", "area")
@@ -105,49 +106,36 @@ def _call(sim: S.Simulation, x03, rows: torch.Tensor) -> None:
     check(L.wl_band_loads(wt, C.byref(g), S._ptr(flow.p), S._ptr(flow.u), nu, S._ptr(idx), S._ptr(nds), idx.numel(), x03, S._ptr(rows)))
 
 
-class Forces:
+class Forces(_series.Series):
     """Recorder of the loads.  buf: Float64 device buffer [capacity, nleaf+1, 16], slot k = the k-th record; t: host list of
     the times."""
 
     def __init__(self, sim: S.Simulation, x0=None, capacity: int = 256):
-        if capacity < 1:
-            raise ValueError("Forces: capacity must be >= 1")
-        self.D = sim.flow.D
-        self.slab = sim.flow.layout.slab
+        flow = sim.flow
         self.nleaf = nleaf(sim)
+        super().__init__(("Forces", "the recorder was"), flow.D, flow.layout.slab, (self.nleaf + 1, NV), capacity, flow.device)
         self.x0 = _x0(x0, self.D)
         self._x03 = _lib.d3(self.x0)
-        self.buf = torch.zeros((int(capacity), self.nleaf + 1, NV), dtype=torch.float64, device=sim.flow.device)
-        self.t: List[float] = []
 
 
 def record(fr: Forces, sim: S.Simulation) -> None:
     """Append the loads on sim.body: one wl_*_loads call into the next slot of the buffer, no synchronisation for a native
     body.  A full buffer is doubled by a device copy."""
-    if sim.flow.D != fr.D or sim.flow.layout.slab is not fr.slab:
-        raise ValueError("Forces: the flow's dimension or slab differs from the one the recorder was made for")
+    row = _series.next_row(fr, sim.flow.D, sim.flow.layout.slab)
     if nleaf(sim) != fr.nleaf:
         raise ValueError("Forces: the body's number of leaves differs from the one the recorder was made for")
-    k = len(fr.t)
-    if k == fr.buf.shape[0]:
-        grown = torch.empty((2 * k,) + tuple(fr.buf.shape[1:]), dtype=fr.buf.dtype, device=fr.buf.device)
-        grown[:k].copy_(fr.buf)
-        fr.buf = grown
-    _call(sim, fr._x03, fr.buf[k])
+    _call(sim, fr._x03, row)
     fr.t.append(S.time(sim.flow))
 
 
 def series(fr: Forces) -> Tuple[np.ndarray, np.ndarray]:
     """(t[K], values[K, nleaf+1, 16]) of the K records so far (synchronises; on z-slabs every rank must call it: the ranks'
     buffers are added once, here)."""
-    K = len(fr.t)
-    v = combine(_rank_parts(fr.buf[:K].cpu().numpy(), fr.slab))
-    return np.asarray(fr.t, dtype=np.float64), v
+    t, parts = _series.rank_rows(fr)
+    return t, combine(parts)
 
 
-def reset(fr: Forces) -> None:
-    """Forget the records (the buffer keeps its size)."""
-    fr.t = []
+reset = _series.reset
 
 
 def loads(sim: S.Simulation, x0=None) -> Dict[str, object]:

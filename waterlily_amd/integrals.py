@@ -16,15 +16,16 @@ and integrals() combine the ranks at the host, in rank order.
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, List, Sequence, Tuple
+from typing import Dict, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from . import _lib
+from . import _series
 from . import sim as S
 from ._lib import check
-from .probes import _rank_parts
+from ._series import _rank_parts
 
 MAX_COLUMNS = (4, 5)            # divmax, umax: combined by maximum; every other column by addition
 
@@ -60,19 +61,14 @@ def _call(flow: S.Flow, U3, row: torch.Tensor) -> None:
     check(_lib.lib().wl_flow_integrals(S._WLT[flow.T], C.byref(g), S._ptr(flow.u), U3, S._ptr(row)))
 
 
-class Integrals:
+class Integrals(_series.Series):
     """Recorder of the integrals.  buf: Float64 device buffer [capacity, 6+D], row k = the k-th record; t: host list of the
     times."""
 
     def __init__(self, flow: S.Flow, U=None, capacity: int = 256):
-        if capacity < 1:
-            raise ValueError("Integrals: capacity must be >= 1")
-        self.D = flow.D
-        self.slab = flow.layout.slab
+        super().__init__(("Integrals", "the recorder was"), flow.D, flow.layout.slab, (6 + flow.D,), capacity, flow.device)
         self.U = _background(U, flow.D)
         self._U3 = _lib.d3(self.U)
-        self.buf = torch.zeros((int(capacity), 6 + self.D), dtype=torch.float64, device=flow.device)
-        self.t: List[float] = []
 
 
 def columns(ig: Integrals) -> Tuple[str, ...]:
@@ -82,28 +78,18 @@ def columns(ig: Integrals) -> Tuple[str, ...]:
 def record(ig: Integrals, flow: S.Flow) -> None:
     """Append the integrals of flow.u: one wl_flow_integrals call into the next row of the buffer, no synchronisation.  A
     full buffer is doubled by a device copy."""
-    if flow.D != ig.D or flow.layout.slab is not ig.slab:
-        raise ValueError("Integrals: the flow's dimension or slab differs from the one the recorder was made for")
-    k = len(ig.t)
-    if k == ig.buf.shape[0]:
-        grown = torch.empty((2 * k, ig.buf.shape[1]), dtype=ig.buf.dtype, device=ig.buf.device)
-        grown[:k].copy_(ig.buf)
-        ig.buf = grown
-    _call(flow, ig._U3, ig.buf[k])
+    _call(flow, ig._U3, _series.next_row(ig, flow.D, flow.layout.slab))
     ig.t.append(S.time(flow))
 
 
 def series(ig: Integrals) -> Tuple[np.ndarray, np.ndarray]:
     """(t[K], values[K, 6+D]) of the K records so far (synchronises; on z-slabs every rank must call it: the ranks' buffers
     are combined once, here)."""
-    K = len(ig.t)
-    v = combine(_rank_parts(ig.buf[:K].cpu().numpy(), ig.slab))
-    return np.asarray(ig.t, dtype=np.float64), v
+    t, parts = _series.rank_rows(ig)
+    return t, combine(parts)
 
 
-def reset(ig: Integrals) -> None:
-    """Forget the records (the buffer keeps its size)."""
-    ig.t = []
+reset = _series.reset
 
 
 def integrals(flow: S.Flow, U=None) -> Dict[str, float]:

@@ -16,14 +16,16 @@ include/wlhip.h (wl_interp) and csrc/wl_probe.h.  Values are Float64 for Float32
 from __future__ import annotations
 
 import ctypes as C
-from typing import List, Optional, Tuple
+from typing import Optional, Tuple
 
 import numpy as np
 import torch
 
 from . import _lib
+from . import _series
 from . import sim as S
 from ._lib import check
+from ._series import _rank_parts, _rank_sum  # noqa: F401  (imported from here by other modules)
 
 
 def _points(x, D: Optional[int] = None) -> np.ndarray:
@@ -31,27 +33,6 @@ def _points(x, D: Optional[int] = None) -> np.ndarray:
     if X.ndim == 0 or X.ndim > 2 or (D is not None and X.shape[-1] != D):
         raise ValueError(f"points must be D floats or an (M, D) array, got shape {X.shape}")
     return np.ascontiguousarray(X.reshape(-1, X.shape[-1]))
-
-
-def _rank_parts(v: np.ndarray, slab) -> list:
-    """The ranks' arrays in rank order, at the host (one all-gather; [v] when not decomposed)."""
-    if slab is None or slab.size == 1:
-        return [v]
-    import torch.distributed as dist
-    parts = [None] * slab.size
-    dist.all_gather_object(parts, v)
-    return parts
-
-
-def _rank_sum(v: np.ndarray, slab) -> np.ndarray:
-    """Sum of the ranks' arrays (every entry is non-zero on at most its owner), in rank order, at the host."""
-    parts = _rank_parts(v, slab)
-    if len(parts) == 1:
-        return v
-    out = parts[0].copy()
-    for p in parts[1:]:
-        out += p
-    return out
 
 
 def _interp_dev(a: torch.Tensor, ncomp: int, x: torch.Tensor, out: torch.Tensor, ldo: int, D: int) -> None:
@@ -80,33 +61,22 @@ def interp(x, a: torch.Tensor):
     return (float(v[0]) if ncomp == 0 else v[0]) if single else v
 
 
-class Probes:
+class Probes(_series.Series):
     """Point probes of u and p.  points: (M, D) index coordinates (or one point), kept on the device.  series: Float64 device
     buffer [capacity, M, D+1] -- row k holds u_1..u_D, p at every point after the k-th record; t: host list of the times."""
 
     def __init__(self, flow: S.Flow, points, capacity: int = 256):
         X = _points(points, flow.D)
-        if capacity < 1:
-            raise ValueError("Probes: capacity must be >= 1")
-        self.D, self.M = flow.D, X.shape[0]
-        self.slab = flow.layout.slab
+        super().__init__(("Probes", "the probes were"), flow.D, flow.layout.slab, (X.shape[0], flow.D + 1), capacity, flow.device)
+        self.M = X.shape[0]
         self.x = torch.from_numpy(X).to(flow.device)
-        self.buf = torch.zeros((int(capacity), self.M, self.D + 1), dtype=torch.float64, device=flow.device)
-        self.t: List[float] = []
 
 
 def record(pr: Probes, flow: S.Flow) -> None:
     """Append u and p at the points: two wl_interp launches into the next row of the series, no synchronisation.  A full
     buffer is doubled by a device copy."""
-    if flow.D != pr.D or flow.layout.slab is not pr.slab:
-        raise ValueError("Probes: the flow's dimension or slab differs from the one the probes were made for")
-    k = len(pr.t)
-    if k == pr.buf.shape[0]:
-        grown = torch.empty((2 * k,) + tuple(pr.buf.shape[1:]), dtype=pr.buf.dtype, device=pr.buf.device)
-        grown[:k].copy_(pr.buf)
-        pr.buf = grown
+    row = _series.next_row(pr, flow.D, flow.layout.slab)
     if pr.M:
-        row = pr.buf[k]
         g = flow.layout.grid()
         L, t = _lib.lib(), S._WLT[flow.T]
         ld = pr.D + 1
@@ -118,14 +88,11 @@ def record(pr: Probes, flow: S.Flow) -> None:
 def series(pr: Probes) -> Tuple[np.ndarray, np.ndarray]:
     """(t[K], values[K, M, D+1]) of the K records so far (synchronises; on z-slabs every rank must call it: the ranks'
     buffers are summed once, here)."""
-    K = len(pr.t)
-    v = _rank_sum(pr.buf[:K].cpu().numpy(), pr.slab)
-    return np.asarray(pr.t, dtype=np.float64), v
+    t, parts = _series.rank_rows(pr)
+    return t, _series._add(parts)
 
 
-def reset(pr: Probes) -> None:
-    """Forget the records (the buffer keeps its size)."""
-    pr.t = []
+reset = _series.reset
 
 
 class Tracers:

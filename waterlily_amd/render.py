@@ -100,12 +100,17 @@ def _i3(v):
     return (C.c_int32 * 3)(*([int(x) for x in v] + [0] * 3)[:3])
 
 
-def _field_grid(r: Renderer, f: torch.Tensor, vector: bool):
-    D = r.flow.D
-    ref = r.flow.u if vector else r.flow.p
+def _code(table: dict, name) -> int:
+    """the library's number of a kind or mode given by name (a number passes through)"""
+    return table[name] if isinstance(name, str) else int(name)
+
+
+def _field_grid(flow, f: torch.Tensor, vector: bool, who: str):
+    """the grid descriptor of `f`, which must be laid out like the flow's u (vector) or p; who: the class named in the error"""
+    ref = flow.u if vector else flow.p
     if tuple(f.shape) != tuple(ref.shape) or f.stride() != ref.stride() or f.dtype != ref.dtype:
-        raise ValueError(f"Renderer: the field must have the layout of flow.{'u' if vector else 'p'} (use waterlily_amd.sim.like)")
-    return S._grid_of(f, D)
+        raise ValueError(f"{who}: the field must have the layout of flow.{'u' if vector else 'p'} (use waterlily_amd.sim.like)")
+    return S._grid_of(f, flow.D)
 
 
 def _extent(r: Renderer):
@@ -122,8 +127,8 @@ def project(r: Renderer, f: torch.Tensor, kind="scalar", mode: str = "slice", ax
     magnitude), "sum", "mean".  out: the Float64 buffer the image goes to (default: the object's image; image() renders the body mask into
     the object's second one).  On a z-slab the view holds this rank's rows (axis 0, 1) or its partial image (axis 2)."""
     D = r.flow.D
-    k = _KIND[kind] if isinstance(kind, str) else int(kind)
-    g = _field_grid(r, f, vector=(k != R_SCALAR))
+    k = _code(_KIND, kind)
+    g = _field_grid(r.flow, f, k != R_SCALAR, "Renderer")
     n = _extent(r)
     axis = int(axis)
     if D == 2 and axis != 2:

@@ -30,7 +30,7 @@ from . import _lib
 from . import sim as S
 from ._lib import check
 from .mesh import MeshBody
-from .probes import _rank_sum
+from ._series import _rank_sum
 from .stats import weight
 
 COLUMNS = tuple(f"{k}_{a}" for k in ("Fp", "Fv", "Mp", "Mv") for a in "xyz")
