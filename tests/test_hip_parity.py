@@ -9,6 +9,7 @@ Tolerances (stated per test):
     (u,p within solver tolerance 1e-4 abs on r.r);
   * iteration counts (pois.n) must be identical.
 """
+import itertools
 import math
 import os
 
@@ -377,6 +378,51 @@ def test_pcg_without_stored_z_bit_exact(T):
     assert np.array_equal(S.to_host(res[0].x), S.to_host(res[1].x))
     assert np.array_equal(S.to_host(lev_h(res[0]).r), S.to_host(lev_h(res[1]).r))
     same(res[0].x, po.x, exact=False, tol=10 * rtol(T))
+
+
+@pytest.mark.parametrize("T", TYPES)
+@pytest.mark.parametrize("padded", [True, False])
+def test_pcg_every_kernel_choice(T, padded):
+    """One pcg! call (after residual!) on the blob system -- 34^3, uniform rows and rows through the block -- under every
+    combination of the switches that decide which of op_pcg's kernels run and how its dot products are finished:
+    PCG_VEC (16-B vector / scalar range kernels), PCG_DEFER_X (x += alpha*eps in the update / direction kernel),
+    PCG_RECOMPUTE_PRECOND (z' = r*iD stored / recomputed), PCG_RECOMPUTE_AEPS (update reads z / is a second 7-point kernel),
+    PCG_DOTS_IN_KERNEL (finalize launches / in-kernel gates).  Every combination: the oracle's update count, x and r within
+    the tolerance of test_pcg_vcycle_solver.
+    Bit for bit (x, r, eps) against the run with no switch set: every combination that differs from the defaults only in
+    PCG_DEFER_X, PCG_RECOMPUTE_PRECOND or PCG_RECOMPUTE_AEPS (at this size the defaults behave as PCG_VEC = 2,
+    PCG_RECOMPUTE_AEPS = 0, PCG_DOTS_IN_KERNEL = 2): same expressions on the same operands, and at 34^3 every reducing kernel
+    cuts the level into the same 8 x 32 workgroups, so the sums are grouped alike.  Beyond those, PCG_DOTS_IN_KERNEL = 0 is
+    asserted bit for bit as well (all 16 combinations with PCG_VEC = 2): the finalize launch and the in-kernel gate sum the
+    same partials in the same order and apply the same scalar steps.  PCG_VEC = 0 (one partial per 256 cells in index order,
+    another grouping of every sum) is compared to the tolerance only."""
+    keys = (Opt.PCG_VEC, Opt.PCG_DEFER_X, Opt.PCG_RECOMPUTE_PRECOND, Opt.PCG_RECOMPUTE_AEPS, Opt.PCG_DOTS_IN_KERNEL)
+    on = (2, 1, 1, 2, 2)
+
+    def run(values):
+        with S.options(values):
+            po, ph, _ = _blob_system(T, O.MultiLevelPoisson, S.MultiLevelPoisson, padded)
+            S.residual(ph)
+            n = S.pcg(ph)
+        return po, ph, n, [S.to_host(a) for a in (ph.x, lev_h(ph).r, lev_h(ph).eps)]
+
+    po, _, n_def, base = run({})
+    O.residual(po)
+    n_o = O.pcg(po)
+    assert n_def == n_o == 6
+    failures = []
+    for combo in itertools.product(*[(v, 0) for v in on]):
+        _, ph, n, got = run(dict(zip(keys, combo)))
+        bits = all(np.array_equal(a, b) for a, b in zip(got, base))
+        scale = [max(1e-30, float(np.max(np.abs(h)))) for h in (po.x, lev_o(po).r)]
+        err = [float(np.max(np.abs(g.astype(np.float64) - h.astype(np.float64)))) / s for g, h, s in zip(got, (po.x, lev_o(po).r), scale)]
+        print(f"{np.dtype(T).name} padded={padded} {dict(zip((k.name for k in keys), combo))}: n={n} bit-equal={bits} "
+              f"err x={err[0]:.2e} r={err[1]:.2e}")
+        if n != n_o or max(err) > rtol(T):
+            failures.append((combo, "oracle", n, err))
+        if combo[0] == 2 and not bits:
+            failures.append((combo, "bits differ from the default run"))
+    assert not failures, failures
 
 
 @pytest.mark.parametrize("T", TYPES)

@@ -363,7 +363,7 @@ template <class T, int D> static int mg_log_row(wl_mg *m, int n, bool have_r2) {
     if (!have_r2) WL_TRY((op_L2<T, D>(lvl<T>(m, 0), m->sc.partials.get(), m->sc.st.get(), false)));
     WL_TRY((mg_Linf<T, D>(m, 0)));
     WL_TRY(m->sc.fetch());
-    m->log.push_back((double)n); m->log.push_back(m->sc.hst.get()->out[1]); m->log.push_back(m->sc.hst.get()->r2);
+    m->log.push_back((double)n); m->log.push_back(m->sc.hst.get()->out[1]); m->log.push_back(m->sc.hst.get()->pcg.r2);
     return 0;
 }
 template <class T, int D> static int mg_solve(wl_mg *m, double tol, int itmx, int *n_iter, const T *divu = nullptr, const G *gu = nullptr,
@@ -379,7 +379,7 @@ template <class T, int D> static int mg_solve(wl_mg *m, double tol, int itmx, in
         WL_TRY((op_L2<T, D>(p, m->sc.partials.get(), m->sc.st.get(), true)));
         WL_TRY(m->sc.fetch());
         ++n;
-        const double r2 = m->sc.hst.get()->r2;
+        const double r2 = m->sc.hst.get()->pcg.r2;
         if (m->log_on) WL_TRY((mg_log_row<T, D>(m, n, true)));
         if (r2 < tol) break;
     }
@@ -1278,7 +1278,7 @@ int wl_mg_pcg(wl_mg *m, int level, int it, int *n_updates) {
     if (rc) return rc;
     if (n_updates) {
         WL_TRY(m->sc.fetch());
-        *n_updates = m->sc.hst.get()->nupd;
+        *n_updates = m->sc.hst.get()->pcg.nupd;
     }
     return 0;
 }
@@ -1305,7 +1305,7 @@ int wl_mg_L2(wl_mg *m, int level, double *out) {
     int rc = [&]() -> int { WL_MG_DISPATCH((op_L2<T, DD>(lvl<T>(m, level), m->sc.partials.get(), m->sc.st.get()))); }();
     if (rc) return rc;
     WL_TRY(m->sc.fetch());
-    *out = m->sc.hst.get()->r2;
+    *out = m->sc.hst.get()->pcg.r2;
     return 0;
 }
 int wl_mg_Linf(wl_mg *m, int level, double *out) {

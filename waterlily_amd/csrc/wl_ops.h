@@ -14,16 +14,11 @@ namespace wl {
 
 // device-resident solver scalars (no host round trip inside pcg!/residual!)
 struct State {
-    double rho, alpha, beta;  // pcg scalars, each holding a value already rounded to T
+    PcgS pcg;                 // pcg!'s scalars and L2(p) as the host, op_L2 and the scalar kernels read them (wl_pcg_scalars.h)
     double shift;             // residual! mean
-    double r2;                // L2(p)
     double out[4];            // generic scalar outputs (cfl dt, dot, sum, ...)
     double red[4];            // reduction staging for the cross-rank all-reduce
-    int active;               // pcg still running
     int do_shift;             // residual! must subtract the mean
-    int nupd;                 // number of (x,r) updates pcg performed
-    int r2_valid;             // the last pcg! update already produced r.r (solver! can skip the separate L2 pass)
-    int xpend;                // pcg stopped at :138 with x += alpha*eps still owed (deferred-x form, see op_pcg)
     PcgS slots[2];            // pcg!'s scalars while its kernels evaluate them themselves (Gate kind 1..4, wl_stencil7.h)
 };
 
@@ -1326,453 +1321,7 @@ _Pragma("unroll")
     });
 }
 
-// pcg!  src/Poisson.jl:123-143 with device-resident rho/alpha/beta and the four early exits turned into a
-// device flag: once `active` drops, the remaining (already enqueued) kernels are no-ops, so no host sync.
-// Fusions: [mult + z.eps], [x,r update + z=r*iD + r.z], [direction]; identical per-cell arithmetic.
-// want_r2: the caller (solver!) needs L2(p) = r.r right after this call; it is accumulated by the last update kernel.
-// Deferred x (WL_OPT_PCG_DEFER_X, default on): in iterations 1..it-1 the update x += alpha*eps (:133) moves from the
-// update kernel into the direction kernel that follows it (which streams eps anyway): one array pass less per
-// iteration (10T instead of 11T for update+direction).  Same per-cell expression, alpha unchanged in between; the :138
-// exit leaves st->xpend so that the direction kernel still applies the owed x update and nothing else.
-// (A variant that folded the direction update into the next mult kernel -- eps_new evaluated on the fly at the 7 stencil
-// points, one array pass less on paper -- was measured slower and removed: see DESIGN.md "measured dead ends".)
-//
-// The function has two independent halves.  WHICH KERNELS run (16-B vector or scalar range kernels; z' stored or
-// recomputed; z = A*eps stored or formed twice) is decided by the switches below.  HOW A DOT PRODUCT IS FINISHED and
-// pcg!'s scalar logic applied (Poisson.jl:127,131-132,135,137-139) is one of three forms, PcgDots:
-//   FINALIZE   a one-workgroup launch after every reducing kernel sums its partials and updates the State; the kernels gate
-//              on st->active (every level when the layout rules out the vector kernels, and the levels above 2^25 cells);
-//   IN_KERNEL  no such launches: the NEXT kernel sums the producer's <= 1024 partials itself in every workgroup and applies the
-//              scalar logic (Gate kind 1..3), the state hops between two slots; one finalize at the end publishes it
-//              (single rank, levels of <= 2^25 cells: -2.8 % per step at 256^3 and below);
-//   SLAB       z-slab levels: the producer's partials are reduced and summed over the ranks (mailbox or ncclAllReduce) into ONE
-//              value, which the consuming kernel's gate treats like a single partial.
-enum class PcgForm { FINALIZE, IN_KERNEL, SLAB };
-template <class T> struct PcgDots {
-    PcgForm form;
-    State *st;
-    double *partials;
-    bool dist, xdef, want_r2;
-    T eps10;
-    int f32, zcap;
-    double *P0, *PA, *PB;   // partials of rho (init) / z.eps (mult) / r.z' or r.r (update); one buffer in the FINALIZE form
-    int cur = 0;            // the slot of st->slots holding the current state (IN_KERNEL, SLAB)
-    PcgDots(PcgForm f, State *st_, double *partials_, bool dist_, bool xdef_, bool want_r2_, T eps10_, int zcap_)
-        : form(f), st(st_), partials(partials_), dist(dist_), xdef(xdef_), want_r2(want_r2_), eps10(eps10_), f32(sizeof(T) == 4), zcap(zcap_) {
-        const bool own = f != PcgForm::FINALIZE;
-        P0 = partials; PA = own ? partials + WL_MAXB : partials; PB = own ? partials + 2 * WL_MAXB : partials;
-    }
-    Gate base() const { Gate g; g.eps10 = (double)eps10; g.f32 = f32; g.zcap = zcap; return g; }
-    // SLAB: the producer's partials become the one value summed over the ranks
-    int ready(const double *&part, int &n) const {
-        if (form != PcgForm::SLAB) return 0;
-        Prof pr(WL_K_SCALAR, 0);
-        WL_TRY((reduce_allreduce<1>(part, n, (int)RED_SUM, 0.0, st->red)));
-        part = st->red;
-        n = 1;
-        return 0;
-    }
-    // ---- after the init kernel (rho = r.z, :126-127)
-    int after_init(int np) const {
-        if (form != PcgForm::FINALIZE) return 0;
-        State *s = st;
-        const T e10 = eps10;
-        return launch_finalize<1>(dist, partials, np, RED_SUM, 0.0, st->red, [=] __device__(const double *v) {
-            const T rho = (T)v[0];
-            s->rho = (double)rho;
-            s->nupd = 0;
-            s->r2_valid = 0;
-            s->xpend = 0;
-            s->active = !((rho < 0 ? -rho : rho) < e10);
-        });
-    }
-    // ---- the gate of mult number n (it finishes rho when n == 1), then what follows the kernel (alpha, :131-132)
-    int gate_mult(int n, int np0, Gate &g) {
-        g = base();
-        if (form == PcgForm::FINALIZE) { g.active = &st->active; return 0; }
-        if (n == 1) {
-            const double *gp = P0; int gn = np0;
-            WL_TRY(ready(gp, gn));
-            g.kind = 1; g.part = gp; g.np = gn; g.out = &st->slots[0]; cur = 0;
-        } else { g.kind = 4; g.in = &st->slots[cur]; }
-        return 0;
-    }
-    int after_mult(int np) const {
-        if (form != PcgForm::FINALIZE) return 0;
-        State *s = st;
-        return launch_finalize<1>(dist, partials, np, RED_SUM, 0.0, st->red, [=] __device__(const double *v) {
-            s->xpend = 0;   // any owed x update was applied by the direction kernel before this mult
-            if (!s->active) return;
-            const T alpha = (T)s->rho / (T)v[0];
-            const double aa = (double)(alpha < 0 ? -alpha : alpha);
-            s->alpha = (double)alpha;
-            if (aa < 1e-2 || aa > 1e2) s->active = 0;  // :132
-        });
-    }
-    // ---- the update kernel's gate (it finishes z.eps), then what follows it (rho2 / beta, :135,137-139; r.r after the last)
-    int gate_update(int npA, Gate &g) {
-        g = base();
-        if (form == PcgForm::FINALIZE) { g.active = &st->active; g.s0 = &st->alpha; return 0; }
-        const double *gp = PA; int gn = npA;
-        WL_TRY(ready(gp, gn));
-        g.kind = 2; g.part = gp; g.np = gn; g.in = &st->slots[cur]; g.out = &st->slots[cur ^ 1];
-        return 0;
-    }
-    void launched_update() { if (form != PcgForm::FINALIZE) cur ^= 1; }
-    int after_update(int np, bool last, bool xnow) const {
-        State *s = st;
-        const bool wr2 = want_r2;
-        if (form != PcgForm::FINALIZE) {
-            if (!last) return 0;
-            const int cs = cur;   // the one finalize of the call: finishes r.r (:135) and publishes the state for the host / L2
-            return launch_finalize<1>(dist, PB, np, RED_SUM, 0.0, st->red, [=] __device__(const double *v) {
-                PcgS sl = s->slots[cs];
-                if (sl.active) {
-                    sl.nupd += 1;
-                    if (wr2) { sl.r2 = (double)(T)v[0]; sl.r2_valid = 1; }
-                    sl.active = 0;
-                }
-                s->rho = sl.rho; s->alpha = sl.alpha; s->beta = sl.beta;
-                s->active = sl.active; s->xpend = sl.xpend; s->nupd = sl.nupd;
-                s->r2_valid = sl.r2_valid;
-                if (sl.r2_valid) s->r2 = sl.r2;
-            });
-        }
-        const T e10 = eps10;
-        return launch_finalize<1>(dist, partials, np, RED_SUM, 0.0, st->red, [=] __device__(const double *v) {
-            if (!s->active) return;
-            s->nupd += 1;
-            if (last) {  // :135
-                if (wr2) { s->r2 = (double)(T)v[0]; s->r2_valid = 1; }
-                s->active = 0;
-                return;
-            }
-            const T rho2 = (T)v[0];
-            if ((rho2 < 0 ? -rho2 : rho2) < e10) { s->active = 0; s->xpend = !xnow; return; }  // :138
-            s->beta = (double)(rho2 / (T)s->rho);
-            s->rho = (double)rho2;
-        });
-    }
-    // ---- the direction kernel's gate (it finishes r.z')
-    int gate_direction(int npB, Gate &g) {
-        g = base();
-        if (form == PcgForm::FINALIZE) {
-            g.active = &st->active; g.also = xdef ? &st->xpend : nullptr; g.s0 = &st->alpha; g.s1 = &st->beta;
-            return 0;
-        }
-        const double *gp = PB; int gn = npB;
-        WL_TRY(ready(gp, gn));
-        g.kind = 3; g.part = gp; g.np = gn; g.in = &st->slots[cur]; g.out = &st->slots[cur ^ 1]; g.also_x = 1;
-        return 0;
-    }
-    void launched_direction() { if (form != PcgForm::FINALIZE) cur ^= 1; }
-};
-
-// WL_OPT_PCG_RECOMPUTE_AEPS on a level of `cells` interior cells: 1 (default) = levels of 2^22 .. 2^26 cells, 3 = every level
-// below 2^26, 2 = every level, 0 = never
-inline bool pcg_recompute_aeps(long cells) {
-    const int v = opt(WL_OPT_PCG_RECOMPUTE_AEPS);
-    return v == 2 || (v == 3 && cells < (1L << 26)) || (v == 1 && cells < (1L << 26) && cells >= (1L << 22));
-}
-// WL_OPT_PCG_DOTS_IN_KERNEL: 1 (default) = on levels of at most 2^25 cells, 2 = on every level, 0 = never; a z-slab run
-// (distr: the sums cross the ranks between the kernels either way) takes any non-zero value
-inline bool pcg_dots_in_kernel(long cells, bool distr) {
-    const int v = opt(WL_OPT_PCG_DOTS_IN_KERNEL);
-    return distr ? v != 0 : (v == 2 || (v == 1 && cells <= (1L << 25)));
-}
-
-template <class T, int D>
-int op_pcg(const LevelT<T> &p, int it, int permask, double *partials, State *st, bool want_r2 = false,
-           int pre_np = -1,     // pre_np >= 0: eps = r*iD and the partials of rho are already there (op_prolong_increment_fused)
-           bool ghost_z = false) {   // z's ghost cells may hold non-zero values (level 1: z is flow.sigma, see op_sigma_ghosts)
-    const LevelT<T> q = p;
-    const Range R = r_inside(p.g);
-    using VA = VecA<T>;
-    const int n0 = p.g.n[0];
-    // ---- which kernels
-    // streaming pcg kernels in 16-B vector form where the layout allows (WL_OPT_PCG_VEC = 0: scalar range kernels)
-    bool vec = false;
-    if constexpr (D == 3) vec = pcg_vec_ok<T>(p.g);
-    const bool xdef = opt(WL_OPT_PCG_DEFER_X) != 0;
-    // z' = r*iD (:136) is not stored (WL_OPT_PCG_RECOMPUTE_PRECOND, default on): the direction kernel recomputes it from r
-    // and iD (iD is a row constant away from the body), one array write + one read less per iteration; z keeps A*eps.
-    const bool zrec = opt(WL_OPT_PCG_RECOMPUTE_PRECOND) != 0;
-    // z = A*eps is not stored either (pcg_recompute_aeps; 3-D vector kernels): the update kernel is a second 7-point kernel
-    // over eps that forms the same A*eps again (same expression, same operands => same bits) and applies
-    // r -= alpha*(A*eps) in its epilogue.  Per iteration one array write (mult) and one array read (update) are replaced
-    // by a second read of eps (with its halo rows and planes).  Measured: 512^3 mult 0.303 -> 0.224 ms but update
-    // 0.344 -> 0.449 ms (the 7-point form of the update runs at 4.1 TB/s): no gain; 256^3 as the finest level: -2.5 % per
-    // step; levels of 128^3 cells and below are latency-bound and lose 5-10 % of a pcg! call to the heavier update kernel
-    // (tools/midlevels.py PCG_RECOMPUTE_AEPS=3,0: 194 / 175, 110 / 101, 77 / 72 us).
-    bool zst = false;
-    if constexpr (D == 3) zst = pcg_recompute_aeps(R.count()) && vec && zrec;
-    // ---- how the dot products are finished (PcgDots above).  The in-kernel sums want few partials: the kernels of such a
-    // call cut z into at most `zcap` chunks (Gate::zcap); levels above 2^25 cells keep the finalize launches
-    // (pcg_dots_in_kernel): there the cap costs the streaming kernels more than the launches it saves (512^3: +0.8 %).
-    const int tpp_v = D == 3 ? (((p.g.n[0] - 2 + 64 * VA::V - 1) / (64 * VA::V)) * ((p.g.n[1] - 2 + 3) / 4) + 7) / 8 * 8 : 0;
-    const bool distr = p.g.dist && ctx().comm && ctx().comm->size > 1;
-    const bool gates = vec && xdef && zrec && R.count() > 0 && tpp_v > 0 && pcg_dots_in_kernel(R.count(), distr) &&
-                       (distr || tpp_v <= WL_PCG_PARTIALS);
-    const PcgForm form = !gates ? PcgForm::FINALIZE : (distr ? PcgForm::SLAB : PcgForm::IN_KERNEL);
-    const int zcap = form == PcgForm::IN_KERNEL ? std::max(WL_PCG_PARTIALS / std::max(tpp_v, 1), 1) : 0;
-    PcgDots<T> dots(form, st, partials, p.g.dist, xdef, want_r2, (T)10 * Lim<T>::eps, zcap);
-    const bool own = form != PcgForm::FINALIZE;   // the vector kernels must take the launch: the gates live in them
-    int np = 0, np0 = 0, npA = 0;
-
-    // ---- :125-127  eps = z = r*iD ; rho = r.z
-    int rv0 = -1;
-    if (pre_np >= 0) { rv0 = 0; np = np0 = pre_np; }
-    else if (vec) {
-        Gate gate_init = dots.base();
-        rv0 = launch_rowvec<T, 1, true>(WL_K_PCG_INIT, p.g,
-            [=] __device__(long o, int, int, const Pre &) { return VA::load(q.r + o); },
-            [=] __device__(long o, int i, int, int, const VA &rr, const auto &rk, double *acc, const Pre &) {
-                const VA id = row_iD<T>(rk, q.iD, o, i, n0);
-                VA zv;
-_Pragma("unroll")
-                for (int v = 0; v < VA::V; ++v) { zv.v[v] = rr.v[v] * id.v[v]; acc[0] += (double)rr.v[v] * (double)zv.v[v]; }
-                if (!zrec) zv.store(q.z + o);
-                zv.store(q.eps + o);
-            }, p.rowc, dots.P0, &np, gate_init);
-        if (rv0 > 0) return rv0;
-        np0 = np;
-    }
-    if (own && rv0 != 0) return fail(WL_E_STATE, "pcg: vector init kernel rejected", __FILE__, __LINE__);
-    if (rv0 != 0)
-    WL_TRY((launch_range_red<1>(WL_K_PCG_INIT, R, [=] __device__(int i, int j, int k, double(&acc)[1]) {
-        const long I = q.g.at(i, j, k);
-        const T v = q.r[I] * q.iD[I];
-        if (!zrec) q.z[I] = v;
-        q.eps[I] = v;
-        acc[0] += (double)q.r[I] * (double)v;
-    }, partials, RED_SUM, 0.0, &np)));
-    WL_TRY(dots.after_init(np));
-
-    for (int n = 1; n <= it; ++n) {
-        const bool last = (n == it);
-        const bool xnow = last || !xdef;   // x += alpha*eps in the update kernel (else in the direction kernel)
-        // ---- :129-131  perBC!(eps) ; z = A eps ; z.eps
-        WL_TRY((op_bc_per<T, D>(p.g, p.eps, permask, false)));  // (x/y copies; the z-slab halo exchange follows)
-        bool exchanged = false;
-        int rcv = -1;
-        if constexpr (D == 3) {
-            if (stencil7_ok<T>(p.g)) {
-                exchanged = true;
-                Gate gate_mult;
-                WL_TRY(dots.gate_mult(n, np0, gate_mult));
-                rcv = launch_stencil7_halo<T, 1>(WL_K_PCG_MULT, p.g, p.eps, SrcArray<T>{p.eps}, p.L, p.rowc, (const T *)nullptr, (const T *)nullptr,
-                    [=] __device__(long o, int, int, int, const VA &ae, const VA &ec, const VA &, const VA &, const auto &, double *acc, const Pre &) {
-                    if (!zst) ae.store(q.z + o);
-_Pragma("unroll")
-                    for (int v = 0; v < VA::V; ++v) acc[0] += (double)ae.v[v] * (double)ec.v[v];
-                }, dots.PA, &np, gate_mult);
-                if (rcv > 0) return rcv;
-                if (own && rcv != 0) return fail(WL_E_STATE, "pcg: vector mult kernel rejected", __FILE__, __LINE__);
-            }
-        }
-        if (!exchanged) WL_TRY((halo_exchange<T>(p.g, p.eps, 1, 1)));
-        if (rcv != 0)
-        WL_TRY((launch_range_red<1>(WL_K_PCG_MULT, R, [=] __device__(int i, int j, int k, double(&acc)[1]) {
-            if (!st->active) return;
-            const long I = q.g.at(i, j, k);
-            const T v = mult1r<T, D>(q.g, q.L, q.eps, I);
-            q.z[I] = v;
-            acc[0] += (double)v * (double)q.eps[I];
-        }, partials, RED_SUM, 0.0, &np)));
-        if (ghost_z && permask != 0) {
-            // z⋅ϵ is a whole-array dot (Poisson.jl:131).  ϵ's ghost cells are zero except in the planes perBC! fills (:129), and
-            // there z may be non-zero: on level 1 z is flow.σ, whose top ghost cells keep conv_diff!'s flux scratch.  Surface sum
-            // over the periodic planes, appended to the partials of the interior sum.
-            int planes = 0, nps = 0;
-            for (int j = 0; j < D; ++j) if ((permask >> j) & 1) planes |= 3 << (2 * j);
-            const G gg = p.g;
-            WL_TRY((launch_shell_red(WL_K_PCG_MULT, p.g, planes, [=] __device__(int i, int j, int k, double(&acc)[1]) {
-                const long I = gg.at(i, j, k);
-                acc[0] += (double)q.z[I] * (double)q.eps[I];
-            }, (rcv == 0 ? dots.PA : partials) + np, RED_SUM, 0.0, &nps, own ? 32 : 256)));
-            np += nps;
-        }
-        npA = np;
-        WL_TRY(dots.after_mult(np));
-
-        // ---- :133-137  x += alpha eps (now or deferred) ; r -= alpha z ; z' = r*iD ; r.z'  (last iteration: r.r)
-        int rvu = -1;
-        Gate gate_upd;
-        WL_TRY(dots.gate_update(npA, gate_upd));
-        if constexpr (D == 3) {
-            if (zst) {   // 7-point kernel over eps: Ae == the z the mult kernel would have stored; a = r, b = x (when x is due)
-                auto upd_epi = [=] __device__(long o, int i, int, int, const VA &ae, const VA &ec, const VA &r0, const VA &x0, const auto &rk, double *acc, const Pre &pre) {
-                    const T alpha = (T)pre.s0;
-                    VA rr = r0;
-                    if (xnow) {
-                        VA xv = x0;
-_Pragma("unroll")
-                        for (int v = 0; v < VA::V; ++v) xv.v[v] += alpha * ec.v[v];
-                        xv.store(q.x + o);
-                    }
-_Pragma("unroll")
-                    for (int v = 0; v < VA::V; ++v) rr.v[v] = rr.v[v] - alpha * ae.v[v];
-                    rr.store(q.r + o);
-                    if (!last) {
-                        const VA id = row_iD<T>(rk, q.iD, o, i, n0);
-_Pragma("unroll")
-                        for (int v = 0; v < VA::V; ++v) { const T zn = rr.v[v] * id.v[v]; acc[0] += (double)rr.v[v] * (double)zn; }
-                    } else if (want_r2) {
-_Pragma("unroll")
-                        for (int v = 0; v < VA::V; ++v) acc[0] += (double)rr.v[v] * (double)rr.v[v];
-                    }
-                };
-                const T *xin = xnow ? (const T *)q.x : (const T *)nullptr;
-                rvu = launch_stencil7<T, 1>(WL_K_PCG_UPDATE, p.g, SrcArray<T>{p.eps}, p.L, p.rowc, (const T *)q.r, xin, upd_epi, dots.PB, &np, gate_upd);
-                if (rvu != 0) return rvu > 0 ? rvu : fail(WL_E_STATE, "pcg: 7-point update kernel rejected", __FILE__, __LINE__);
-                dots.launched_update();
-            }
-        }
-        if (vec && rvu != 0) {
-            struct UD { VA r, z, x, e; };
-            rvu = launch_rowvec<T, 1, true>(WL_K_PCG_UPDATE, p.g,
-                [=] __device__(long o, int, int, const Pre &) {
-                    UD d;
-                    d.r = VA::load(q.r + o);
-                    d.z = VA::load(q.z + o);
-                    if (xnow) { d.x = VA::load(q.x + o); d.e = VA::load(q.eps + o); }
-                    return d;
-                },
-                [=] __device__(long o, int i, int, int, const UD &d, const auto &rk, double *acc, const Pre &pre) {
-                    const T alpha = (T)pre.s0;
-                    VA rr = d.r;
-                    if (xnow) {
-                        VA xv = d.x;
-_Pragma("unroll")
-                        for (int v = 0; v < VA::V; ++v) xv.v[v] += alpha * d.e.v[v];
-                        xv.store(q.x + o);
-                    }
-_Pragma("unroll")
-                    for (int v = 0; v < VA::V; ++v) rr.v[v] = rr.v[v] - alpha * d.z.v[v];
-                    rr.store(q.r + o);
-                    if (!last) {
-                        const VA id = row_iD<T>(rk, q.iD, o, i, n0);
-                        VA zn;
-_Pragma("unroll")
-                        for (int v = 0; v < VA::V; ++v) { zn.v[v] = rr.v[v] * id.v[v]; acc[0] += (double)rr.v[v] * (double)zn.v[v]; }
-                        if (!zrec) zn.store(q.z + o);   // (else) the direction kernel recomputes r*iD: z' is never stored
-                    } else if (want_r2) {
-_Pragma("unroll")
-                        for (int v = 0; v < VA::V; ++v) acc[0] += (double)rr.v[v] * (double)rr.v[v];
-                    }
-                }, p.rowc, dots.PB, &np, gate_upd);
-            if (rvu > 0) return rvu;
-            if (own && rvu != 0) return fail(WL_E_STATE, "pcg: vector update kernel rejected", __FILE__, __LINE__);
-            if (rvu == 0) dots.launched_update();
-        }
-        if (rvu != 0)
-        WL_TRY((launch_range_red<1>(WL_K_PCG_UPDATE, R, [=] __device__(int i, int j, int k, double(&acc)[1]) {
-            if (!st->active) return;
-            const long I = q.g.at(i, j, k);
-            const T alpha = (T)st->alpha;
-            if (xnow) q.x[I] += alpha * q.eps[I];
-            const T rn = q.r[I] - alpha * q.z[I];
-            q.r[I] = rn;
-            if (!last) {
-                const T zn = rn * q.iD[I];
-                if (!zrec) q.z[I] = zn;
-                acc[0] += (double)rn * (double)zn;
-            } else if (want_r2) {
-                acc[0] += (double)rn * (double)rn;
-            }
-        }, partials, RED_SUM, 0.0, &np)));
-        WL_TRY(dots.after_update(np, last, xnow));
-        if (last) break;
-
-        // ---- :140  eps = beta eps + z'  (+ the deferred x += alpha eps)
-        int rvd = -1;
-        Gate gate_dir;
-        WL_TRY(dots.gate_direction(np, gate_dir));
-        if (vec) {
-            struct DD { VA e, x, z; };
-            rvd = launch_rowvec<T, 0, true>(WL_K_PCG_DIR, p.g,
-                // gate: runs when pcg is active, or (deferred x) when only the x update of the :138 exit is owed
-                [=] __device__(long o, int, int, const Pre &pre) {
-                    DD d;
-                    d.e = VA::load(q.eps + o);
-                    if (xdef) d.x = VA::load(q.x + o);
-                    if (pre.act) d.z = VA::load((zrec ? q.r : q.z) + o);
-                    return d;
-                },
-                [=] __device__(long o, int i, int, int, const DD &d, const auto &rk, double *, const Pre &pre) {
-                    VA ev = d.e, zv = VA::splat((T)0);
-                    if (pre.act) {
-                        zv = d.z;
-                        if (zrec) {   // z' = r*iD (:136) recomputed
-                            const VA id = row_iD<T>(rk, q.iD, o, i, n0);
-_Pragma("unroll")
-                            for (int v = 0; v < VA::V; ++v) zv.v[v] = d.z.v[v] * id.v[v];
-                        }
-                    }
-                    if (xdef) {   // :133, deferred from the update kernel
-                        const T alpha = (T)pre.s0;
-                        VA xv = d.x;
-_Pragma("unroll")
-                        for (int v = 0; v < VA::V; ++v) xv.v[v] += alpha * ev.v[v];
-                        xv.store(q.x + o);
-                    }
-                    if (!pre.act) return;
-                    const T beta = (T)pre.s1;
-_Pragma("unroll")
-                    for (int v = 0; v < VA::V; ++v) ev.v[v] = beta * ev.v[v] + zv.v[v];
-                    ev.store(q.eps + o);
-                }, p.rowc, nullptr, nullptr, gate_dir);
-            if (rvd > 0) return rvd;
-            if (own && rvd != 0) return fail(WL_E_STATE, "pcg: vector direction kernel rejected", __FILE__, __LINE__);
-            if (rvd == 0) dots.launched_direction();
-        }
-        if (rvd != 0)
-        WL_TRY(launch_range(WL_K_PCG_DIR, R, [=] __device__(int i, int j, int k) {
-            const int act = st->active;
-            if (!act && !(xdef && st->xpend)) return;
-            const long I = q.g.at(i, j, k);
-            if (xdef) {
-                q.x[I] += (T)st->alpha * q.eps[I];
-                if (!act) return;
-            }
-            q.eps[I] = (T)st->beta * q.eps[I] + (zrec ? q.r[I] * q.iD[I] : q.z[I]);
-        }));
-    }
-    return 0;
-}
-
-// L2(p) = r.r  src/Poisson.jl:146 -> st->r2.  after_pcg: skip the work when the pcg! call just before already
-// produced it (st->r2_valid, see op_pcg want_r2); the kernels are still enqueued (no host decision) but return at once.
-template <class T, int D>
-int op_L2(const LevelT<T> &p, double *partials, State *st, bool after_pcg = false) {
-    const LevelT<T> q = p;
-    int np = 0;
-    int rcv = -1;
-    if constexpr (D == 3) {
-        if (pcg_vec_ok<T>(p.g)) {   // 16-B streaming form; when the pcg! before it already produced r.r the
-            using VA = VecA<T>;                      // gate closes and every workgroup leaves at once
-            Gate gate;
-            if (after_pcg) { gate.active = &st->r2_valid; gate.inv = 1; }
-            rcv = launch_rowvec<T, 1, false>(WL_K_DOT, p.g,
-                [=] __device__(long o, int, int, const Pre &) { return VA::load(q.r + o); },
-                [=] __device__(long, int, int, int, const VA &rr, const auto &, double *acc, const Pre &) {
-_Pragma("unroll")
-                    for (int v = 0; v < VA::V; ++v) acc[0] += (double)rr.v[v] * (double)rr.v[v];
-                }, (const T *)nullptr, partials, &np, gate);
-            if (rcv > 0) return rcv;
-        }
-    }
-    if (rcv != 0)
-    WL_TRY((launch_range_red<1>(WL_K_DOT, r_inside(p.g), [=] __device__(int i, int j, int k, double(&acc)[1]) {
-        if (after_pcg && st->r2_valid) return;
-        const double v = (double)q.r[q.g.at(i, j, k)];
-        acc[0] += v * v;
-    }, partials, RED_SUM, 0.0, &np)));
-    return launch_finalize<1>(p.g.dist, partials, np, RED_SUM, 0.0, st->red, [=] __device__(const double *v) {
-        if (after_pcg && st->r2_valid) return;
-        st->r2 = (double)(T)v[0];
-    });
-}
+// pcg! and L2 (src/Poisson.jl:123-143,146): wl_pcg.h, included at the end of this file
 
 // ------------------------------------------------------------------------------------------ MultiLevelPoisson.jl
 // interior coarse cells whose 2^D children (up(I), MultiLevelPoisson.jl:1) are all OWNED fine cells of this rank.
@@ -1859,3 +1408,5 @@ int op_prolongate(const G &ga, T *a, const G &gb, const T *b) {
 }
 
 }  // namespace wl
+
+#include "wl_pcg.h"

@@ -30,6 +30,7 @@
 #include <type_traits>
 
 #include "wl_common.h"
+#include "wl_pcg_scalars.h"
 
 namespace wl {
 
@@ -73,12 +74,11 @@ constexpr int S7_BY = 4;   // wavefronts per workgroup of the vector kernels
 //           optional device scalars (alpha, beta) handed to the functor.
 //   kind 1..4 (pcg! without the one-workgroup finalize launches): the kernel ITSELF finishes the dot product of the
 //           kernel before it -- every workgroup sums that kernel's per-workgroup partials in the fixed order of k_finalize
-//           (<= 1024 doubles, L2-resident) and applies pcg!'s scalar logic (src/Poisson.jl:127,131-132,137-139) to the
+//           (<= 1024 doubles, L2-resident) and applies pcg!'s scalar logic (wl_pcg_scalars.h) to the
 //           state it reads from slot `in`; the first thread of the grid stores the new state to the OTHER slot `out`
 //           (nobody reads that one during this kernel), from where the next kernel picks it up.
 //           1: after the init kernel (rho, :126-127)   2: after mult (alpha, :131-132)
-//           3: after a non-final update (rho2, beta, :137-139)   4: read the state only
-struct PcgS { double rho, alpha, beta, r2; int active, xpend, nupd, r2_valid; };
+//           3: after a non-final update (new rho, beta, :137-139)   4: read the state only
 struct Gate {
     const int *active = nullptr, *also = nullptr;
     const double *s0 = nullptr, *s1 = nullptr;
@@ -99,31 +99,6 @@ struct Gate {
 // 128 / 256 / 512 / 1024 / 2048)
 constexpr int WL_PCG_PARTIALS = 1024;
 struct Pre { int act; double s0, s1; };
-// pcg!'s scalar logic, shared by the in-kernel form (gate_open) and the k_finalize epilogues of op_pcg
-__device__ __forceinline__ double pcg_rnd(double x, int f32) { return f32 ? (double)(float)x : x; }
-__device__ __forceinline__ double pcg_div(double a, double b, int f32) { return f32 ? (double)((float)a / (float)b) : a / b; }
-__device__ __forceinline__ void pcg_after_init(PcgS &s, double v, double eps10, int f32) {
-    const double rho = pcg_rnd(v, f32);
-    s.rho = rho; s.alpha = 0.0; s.beta = 0.0; s.r2 = 0.0;
-    s.nupd = 0; s.r2_valid = 0; s.xpend = 0;
-    s.active = !((rho < 0 ? -rho : rho) < eps10);
-}
-__device__ __forceinline__ void pcg_after_mult(PcgS &s, double v, int f32) {
-    s.xpend = 0;   // any owed x update was applied by the direction kernel before this mult
-    if (!s.active) return;
-    const double alpha = pcg_div(s.rho, pcg_rnd(v, f32), f32);
-    const double aa = alpha < 0 ? -alpha : alpha;
-    s.alpha = alpha;
-    if (aa < 1e-2 || aa > 1e2) s.active = 0;   // :132
-}
-__device__ __forceinline__ void pcg_after_update(PcgS &s, double v, double eps10, int f32, bool xnow) {   // non-final iteration
-    if (!s.active) return;
-    s.nupd += 1;
-    const double rho2 = pcg_rnd(v, f32);
-    if ((rho2 < 0 ? -rho2 : rho2) < eps10) { s.active = 0; s.xpend = !xnow; return; }   // :138
-    s.beta = pcg_div(rho2, s.rho, f32);
-    s.rho = rho2;
-}
 // sum of np partials, same order as k_finalize; 256-thread workgroups, every thread must call; all threads get the value
 __device__ __forceinline__ double block_sum_partials(const double *part, int np) {
     __shared__ double bc;
