@@ -602,6 +602,70 @@ int wl_downsample(wl_dtype t, const wl_grid *g, const void *f, int kind, int ipa
                   int mode, int factor, const int32_t lo[3], const int32_t hi[3], wl_dtype t_out, void *out_dev, int ntuple, int c);
 int wl_downsample_extent(const wl_grid *g, int factor, const int32_t lo[3], const int32_t hi[3], int32_t nc[3], int32_t *k0);
 
+/* ------------------------------------------------------------------ histograms and extremes (Histogram, waterlily_amd/hist.py)
+ * How the values of a field are distributed over the cells lo_d <= J_d < hi_d (0-based, z global): wl_histogram counts one value
+ * per cell into bins (1-D), or a pair of values into a table (joint 2-D); wl_field_range finds the extremes.  The value of a cell
+ * is formed on the fly, as for wl_render_project and wl_downsample (the same device function): no volume is filled first.
+ *   kind  : per axis: WL_R_SCALAR, WL_R_UCOMP, WL_R_CENTRE, WL_R_METRIC + WL_M_* with ipar, par, par2 exactly as for
+ *           wl_render_project; the value is a double, replaced by |v| when absval != 0.  WL_R_FACE is refused.  The two axes of
+ *           a joint histogram may read different fields (a->f = p, b->f = u); both lie on the grid g and have dtype t.
+ *   box   : lo == hi == NULL: inside().  0 <= lo_d < hi_d <= n_d - 1 (nzg - 1 along z); a metric kind's box must lie in inside()
+ *           (of either axis).  D == 2: two entries are read.
+ *   bins  : an axis has n = nbins interior bins 1..n, the underflow bin 0 and the overflow bin n + 1.  A cell whose value on
+ *           either axis is NaN is counted in cnt_dev[1] and in no bin.  For any other v (+-inf included), three ways:
+ *           uniform, host range (range_dev == edges_dev == NULL): lo, hi of the struct, finite, hi > lo.
+ *           uniform, device range (range_dev: two doubles on the device, e.g. wl_field_range's output: an auto-ranged histogram
+ *             needs no read-back): lo = range_dev[0], hi = range_dev[1], read by the kernel.
+ *             Both: v < lo: bin 0; else v > hi: bin n + 1; else, if !(hi > lo) -- only a device range can be so: a constant
+ *             field, or NaN, NaN from a box of nothing but NaN -- bin 1 if lo <= v <= hi and bin n + 1 otherwise (so with a NaN
+ *             range every non-NaN cell is in bin n + 1; nothing is multiplied); else t = (v - lo) * scale with
+ *             scale = (double)n / (hi - lo), every operation an IEEE double operation rounded on its own (no FMA), computed on
+ *             the device in both cases, and the bin is 1 + min(n - 1, (int)t), where a t that is not < n - 1 (NaN from an
+ *             infinite device range included) takes n - 1 without a conversion.  The top edge is closed: v == hi is in bin n.
+ *           edges (edges_dev: n + 1 strictly increasing finite doubles e_0..e_n on the device, n <= 1024): v < e_0: bin 0;
+ *             v > e_n: bin n + 1; else 1 + (the number of e_1..e_{n-1} that are <= v): numpy's convention, bin k = [e_{k-1}, e_k)
+ *             and the last one closed, v == e_n in bin n.  Comparisons only (a binary search over a copy in LDS).  THAT THE
+ *             EDGES INCREASE IS THE CALLER'S PRECONDITION: the library cannot read them before the launch (waterlily_amd.hist
+ *             checks its host copy); edges that do not increase give counts that mean nothing, never an access out of bounds.
+ *   out   : A = a->nbins + 2, B = b ? b->nbins + 2 : 1.  cnt_dev: 2 + A*B int64: [0] the cells visited (the box's cells in
+ *           this rank's planes), [1] the cells dropped for a NaN, [2 + jb*A + ia] the bins: cnt[0] == cnt[1] + the sum of the
+ *           bins.  accumulate == 0: the call overwrites (it zeroes the 2 + A*B entries on the library's stream first);
+ *           accumulate != 0: it adds to what is there (a PDF over many steps).  A*B <= 8192.
+ *   order : none.  Counts are integers: wavefronts count into a workgroup's uint32 table in LDS (a workgroup counts far fewer
+ *           than 2^32 cells: csrc/wl_hist.h) and the workgroups add to cnt_dev with 64-bit integer atomics, so the result is a
+ *           function of the field and the bins alone, bit for bit, on any launch shape.  No floating-point atomics anywhere.
+ *   slabs : a rank counts the cells of the box in the planes it owns (the first rank of a ring also takes the bottom ghost
+ *           plane, as for wl_isosurface); a rank without a plane in the box leaves zeros (accumulate == 0).  The ranks' tables
+ *           added up are the undecomposed table, exactly; nothing is communicated.  A metric kind reads the first halo plane on
+ *           each side, WL_R_CENTRE along z the one above.  A device range is this rank's own: combine ranges before use.
+ * wl_field_range: out_dev[0..3] = the minimum, the maximum, the number of non-NaN cells, the number of NaN cells (doubles; the
+ * counts are exact below 2^53) of the value (kind, ipar, par, par2, absval as above) over the box.  NaN is skipped, +-inf take
+ * part; -0 and +0 compare by the IEEE total order (the minimum of the two is -0, the maximum +0), so the result does not depend
+ * on the order of combination; no non-NaN cell (or no cell of this rank's): NaN, NaN, 0, the NaN cells.  Two launches:
+ * per-workgroup partials into scratch_dev (at least wl_field_range_scratch's bytes: a constant of the library, whatever the
+ * grid), then one workgroup combines them.  No atomics.
+ * Refused with WL_E_ARG before the device is touched: wl_histogram: NULL g, a, a->f, cnt_dev, or b->f of a given b; an unknown
+ * t, kind or component; WL_R_FACE; nbins < 1; A*B > 8192; edges with nbins > 1024; both range_dev and edges_dev; a host range
+ * that is not finite or not hi > lo; only one of lo and hi of the box; a bad box; a metric box outside inside().
+ * wl_field_range: NULL g, f, out_dev or scratch_dev; scratch_bytes too small; t, kind, component and box as above.
+ * wl_field_range_scratch: NULL g or bytes, a bad grid.  Asynchronous on the library's stream: wl_histogram one launch (after a
+ * memset), wl_field_range two; nothing allocated.  WaterLily v1.3 has no such function to override. */
+typedef struct {
+    const void *f;            /* the field this axis reads */
+    int32_t kind, ipar;
+    double par[3], par2[3];   /* of a metric kind (wl_metric); unused otherwise */
+    int32_t absval;
+    int32_t nbins;
+    double lo, hi;            /* the host range; unused with range_dev or edges_dev */
+    const double *range_dev;  /* NULL, or {lo, hi} on the device */
+    const double *edges_dev;  /* NULL, or nbins + 1 edges on the device */
+} wl_hist_axis;
+int wl_histogram(wl_dtype t, const wl_grid *g, const wl_hist_axis *a, const wl_hist_axis *b, const int32_t lo[3], const int32_t hi[3],
+                 int accumulate, int64_t *cnt_dev);
+int wl_field_range(wl_dtype t, const wl_grid *g, const void *f, int kind, int ipar, const double par[3], const double par2[3],
+                   int absval, const int32_t lo[3], const int32_t hi[3], void *scratch_dev, int64_t scratch_bytes, double *out_dev);
+int wl_field_range_scratch(const wl_grid *g, int64_t *bytes);
+
 /* ------------------------------------------------------------------ snapshots (VTK write / restart,ext/WaterLilyWriteVTKExt.jl:57-66,
  * ext/WaterLilyReadVTKExt.jl:28-45).  The reference copies whole fields to the host (`a.flow.u |> Array`) and permutes the vector
  * components to the front there (components_first, :79).  Here the field's LOCAL planes klo..khi are packed on the device into

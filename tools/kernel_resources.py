@@ -54,6 +54,10 @@ def short(d):
         m = re.match(r"(?:float|double), (true|false), (true|false), (\d+)", args)
         if m:
             extra = [f"fuse={m.group(1)}", f"copy={m.group(2)}", f"BY={m.group(3)}"]
+    elif kern in ("k_hist", "k_field_range"):
+        m = re.match(r"(?:float|double), (\d), (true|false)(?:, (\d))?", args)
+        if m:
+            extra = [f"D={m.group(1)}", f"metric={m.group(2)}"] + ([f"B={('none', 'plain', 'metric')[int(m.group(3))]}"] if m.group(3) else [])
     return " ".join(x for x in [kern, T, op.group(1) if op else "", ("#" + lam[0]) if lam else ""] + extra if x)
 
 

@@ -3,6 +3,8 @@ from .body import AutoBody, NoBody, measure, norm2  # noqa: F401
 from .downsample import Downsampler, DownsampleWriter  # noqa: F401
 from . import forces  # noqa: F401
 from .forces import Forces  # noqa: F401
+from . import hist  # noqa: F401
+from .hist import Axis, Histogram  # noqa: F401
 from .mesh import MeshBody  # noqa: F401
 from .probes import Probes, Tracers, interp  # noqa: F401
 from .render import Renderer  # noqa: F401

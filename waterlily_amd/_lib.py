@@ -52,6 +52,13 @@ class MeshPose(C.Structure):
                 ("Ainv", C.c_double * 9), ("identity_map", C.c_int32)]
 
 
+class HistAxis(C.Structure):
+    """wl_hist_axis (include/wlhip.h): one axis of a histogram"""
+    _fields_ = [("f", C.c_void_p), ("kind", C.c_int32), ("ipar", C.c_int32), ("par", C.c_double * 3), ("par2", C.c_double * 3),
+                ("absval", C.c_int32), ("nbins", C.c_int32), ("lo", C.c_double), ("hi", C.c_double), ("range_dev", C.c_void_p),
+                ("edges_dev", C.c_void_p)]
+
+
 WL_BODY_SPHERE, WL_BODY_TORUS, WL_BODY_PLATE, WL_BODY_CYLINDER = 0, 1, 2, 3
 WL_BODY_OP_UNION, WL_BODY_OP_MINUS, WL_BODY_OP_INTERSECT = 0, 1, 2
 WL_BODY_MAXLEAF = 6
@@ -229,6 +236,9 @@ def lib() -> C.CDLL:
         "wl_render_shade": (i, [vp, i64, i, i, d, d, i, vp, vp, i64, d, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), i, i, vp]),
         "wl_downsample": (i, [i, gp, vp, i, i, dp, dp, i, i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), i, vp, i, i]),
         "wl_downsample_extent": (i, [gp, i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+        "wl_histogram": (i, [i, gp, vp, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), i, vp]),      # (a, b: byref(HistAxis))
+        "wl_field_range": (i, [i, gp, vp, i, i, dp, dp, i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, i64, vp]),
+        "wl_field_range_scratch": (i, [gp, C.POINTER(C.c_int64)]),
         "wl_snapshot_pack": (i, [i, gp, vp, i, i, i, i, vp]),
         "wl_snapshot_unpack": (i, [i, gp, vp, i, i, i, i, vp]),
         "wl_set_option": (i, [i, i]),

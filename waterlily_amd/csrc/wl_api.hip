@@ -22,6 +22,7 @@
 #include "wl_iso.h"
 #include "wl_render.h"
 #include "wl_downsample.h"
+#include "wl_hist.h"
 
 namespace wl {
 
@@ -1729,6 +1730,63 @@ int wl_downsample(wl_dtype t, const wl_grid *g, const void *f, int kind, int ipa
         return fail(WL_E_ARG, "wl_downsample: a boundary of this rank's planes inside the box is not at lo_2 + m*factor", __FILE__, __LINE__);
     l[2] = klo;
     WL_DISPATCH(t, D, (op_downsample<T, DD>(gg, (const T *)f, kind, ipar, par, par2, mode, factor, l, nc, t_out == WL_F64, out_dev, ntuple, c)));
+}
+// the checks of one axis of wl_histogram (bins != 0) or of wl_field_range's value (bins == 0)
+static int hist_axis_args(const char *who, const wl_hist_axis *a, int D, bool bins) {
+    WL_TRY(check_kind(who, a->kind, a->ipar, D, false));
+    if (!bins) return 0;
+    if (a->nbins < 1) WL_BAD(who, "nbins must be >= 1");
+    if (a->range_dev && a->edges_dev) WL_BAD(who, "both range_dev and edges_dev given");
+    if (a->edges_dev && a->nbins > HIST_MAXEDGES) WL_BAD(who, "edges take nbins <= 1024");
+    if (!a->range_dev && !a->edges_dev && !(std::isfinite(a->lo) && std::isfinite(a->hi) && a->hi > a->lo))
+        WL_BAD(who, "a host range needs finite lo < hi");
+    return 0;
+}
+// the box of wl_histogram / wl_field_range -> l, h (a box without cells is refused), with a metric kind's two conditions
+static int hist_box_args(const char *who, const G &gg, int D, bool metric, const int32_t lo[3], const int32_t hi[3], int l[3], int h[3]) {
+    WL_TRY(parse_box(who, gg, D, 1, false, lo, hi, l, h));
+    if (metric) WL_TRY(check_metric_box(who, D, l));
+    if (metric) WL_TRY(check_halo_planes(who, gg, false));
+    return 0;
+}
+int wl_histogram(wl_dtype t, const wl_grid *g, const wl_hist_axis *a, const wl_hist_axis *b, const int32_t lo[3], const int32_t hi[3],
+                 int accumulate, int64_t *cnt_dev) {
+    if (!g || !a || !cnt_dev) return fail(WL_E_ARG, "wl_histogram: null grid, axis or counts", __FILE__, __LINE__);
+    WL_TRY(check_grid(g));
+    WL_TRY(check_dtype("wl_histogram", t));
+    if (!a->f || (b && !b->f)) return fail(WL_E_ARG, "wl_histogram: null field of an axis", __FILE__, __LINE__);
+    const int D = g->D;
+    WL_TRY(hist_axis_args("wl_histogram", a, D, true));
+    if (b) WL_TRY(hist_axis_args("wl_histogram", b, D, true));
+    if ((int64_t)(a->nbins + 2LL) * (b ? b->nbins + 2LL : 1LL) > HIST_MAXBINS)
+        return fail(WL_E_ARG, "wl_histogram: more than 8192 bins ((a->nbins + 2) * (b->nbins + 2))", __FILE__, __LINE__);
+    const G gg = mkG(g);
+    int l[3], h[3];
+    WL_TRY(hist_box_args("wl_histogram", gg, D, a->kind >= WL_R_METRIC || (b && b->kind >= WL_R_METRIC), lo, hi, l, h));
+    WL_DISPATCH(t, D, (op_histogram<T, DD>(gg, a, b, l, h, accumulate, cnt_dev)));
+}
+int wl_field_range_scratch(const wl_grid *g, int64_t *bytes) {
+    if (!g || !bytes) return fail(WL_E_ARG, "wl_field_range_scratch: null grid or bytes", __FILE__, __LINE__);
+    WL_TRY(check_grid(g));
+    *bytes = RANGE_SCRATCH;
+    return 0;
+}
+int wl_field_range(wl_dtype t, const wl_grid *g, const void *f, int kind, int ipar, const double par[3], const double par2[3],
+                   int absval, const int32_t lo[3], const int32_t hi[3], void *scratch_dev, int64_t scratch_bytes, double *out_dev) {
+    if (!g || !f || !out_dev) return fail(WL_E_ARG, "wl_field_range: null grid, field or output", __FILE__, __LINE__);
+    WL_TRY(check_grid(g));
+    WL_TRY(check_dtype("wl_field_range", t));
+    const int D = g->D;
+    wl_hist_axis a{};
+    a.f = f; a.kind = kind; a.ipar = ipar; a.absval = absval;
+    for (int d = 0; d < D; ++d) { a.par[d] = par ? par[d] : 0.0; a.par2[d] = par2 ? par2[d] : 0.0; }
+    WL_TRY(hist_axis_args("wl_field_range", &a, D, false));
+    if (!scratch_dev || scratch_bytes < RANGE_SCRATCH)
+        return fail(WL_E_ARG, "wl_field_range: no scratch, or fewer bytes than wl_field_range_scratch asks for", __FILE__, __LINE__);
+    const G gg = mkG(g);
+    int l[3], h[3];
+    WL_TRY(hist_box_args("wl_field_range", gg, D, kind >= WL_R_METRIC, lo, hi, l, h));
+    WL_DISPATCH(t, D, (op_field_range<T, DD>(gg, &a, l, h, scratch_dev, out_dev)));
 }
 int wl_tracer_advance(wl_dtype t, const wl_grid *g, const void *u, double *x_dev, int64_t m, double dt, int perdir_mask) {
     WL_TRY(check_grid(g));

@@ -190,6 +190,20 @@ __global__ __launch_bounds__(256) void k_render_row(const G g, const RenderBox B
     }
 }
 
+// The LOCAL planes klo <= k < khi this rank visits of a box's GLOBAL planes lo2 <= z < hi2: the box, the planes it owns (the
+// first rank of a ring takes the bottom ghost plane, which nobody owns), and the local array -- wl_isosurface's rule.  No plane:
+// khi == klo.
+inline void box_planes(const G &g, int lo2, int hi2, int *klo, int *khi) {
+    int own_lo = g.kz0 + g.zlo, own_hi = g.kz0 + g.zhi;
+    if (g.dist && g.zring && own_lo == 1) own_lo = 0;
+    const int zlo = lo2 > own_lo ? lo2 : own_lo, zhi = hi2 < own_hi + 1 ? hi2 : own_hi + 1;
+    *klo = zlo - g.kz0;
+    *khi = zhi - g.kz0;
+    if (*klo < 0) *klo = 0;
+    if (*khi > g.n[2] - 1) *khi = g.n[2] - 1;
+    if (*khi < *klo) *khi = *klo;
+}
+
 // lo / hi: the box in GLOBAL indices, already validated against the undecomposed extents (D == 2: lo[2] = 0, hi[2] = 1)
 template <class T, int D>
 int op_render_project(const G &g, const T *f, int kind, int ipar, const double *par, const double *par2, int axis, int mode,
@@ -199,17 +213,8 @@ int op_render_project(const G &g, const T *f, int kind, int ipar, const double *
     B.row0 = 0;
     B.cnt = (double)(hi[axis] - lo[axis]);
     if (D == 3) {
-        // planes this rank visits: the box, the planes it owns (the first rank of a ring takes the bottom ghost plane, which
-        // nobody owns), and the local array -- wl_isosurface's rule
-        int own_lo = g.kz0 + g.zlo, own_hi = g.kz0 + g.zhi;
-        if (g.dist && g.zring && own_lo == 1) own_lo = 0;
-        const int zlo = lo[2] > own_lo ? lo[2] : own_lo, zhi = hi[2] < own_hi + 1 ? hi[2] : own_hi + 1;
-        int klo = zlo - g.kz0, khi = zhi - g.kz0;
-        if (klo < 0) klo = 0;
-        if (khi > g.n[2] - 1) khi = g.n[2] - 1;
-        if (khi < klo) khi = klo;
-        B.lo[2] = klo; B.hi[2] = khi;
-        B.row0 = klo + g.kz0 - lo[2];
+        box_planes(g, lo[2], hi[2], &B.lo[2], &B.hi[2]);
+        B.row0 = B.lo[2] + g.kz0 - lo[2];
     }
     RenderWhat w;
     w.kind = kind; w.ipar = ipar; w.mode = mode;
