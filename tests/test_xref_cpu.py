@@ -7,7 +7,7 @@ import pytest
 
 import xref as X
 from oracle import wl_oracle as O
-from xref_inputs import KINDS, coefficients, field, periodic_subsets, step_fields
+from xref_inputs import KINDS, body_block, coefficients, field, periodic_subsets, project_fields, step_fields
 
 TYPES = [np.float32, np.float64]
 K = X.K
@@ -265,24 +265,21 @@ def _oracle_twin_step(a, b, T):
     return up, gc
 
 
-@pytest.mark.parametrize("T", TYPES)
-@pytest.mark.parametrize("dims,perdir", [((20, 12, 8), ()), ((24, 16), ()), ((24, 16), (0,))])
-def test_mom_step_corrector_f_oracle_vs_xref(T, dims, perdir):
-    """After one mom_step! f holds the corrector's BDIM! value u_start + dt*(conv_diff(u') + g_corr) - V (Flow.jl:164-166,
-    :133), K = 12 (xref.mom_f).  u' is taken from the oracle's own operators replayed in mom_step!'s order, held
-    bit-identical to the oracle's step first.  Inputs: a non-uniform u, a body block with V != 0, a time-dependent body
-    force.  Controls: dt off by 64K eps, the samples shifted one plane, u_start replaced by u' must fail."""
+def _oracle_step_and_twin(T, dims, perdir, dt0=0.25, p0=None):
+    """One mom_step! of the oracle on step_fields (a non-uniform u, a body block with V != 0, a time-dependent body force)
+    and its replay from the oracle's operators, held bit-identical: (flow, solver, u', u_start, g_corr, dt)"""
     D = len(dims)
     Ng = tuple(n + 2 for n in dims)
-    tn = np.dtype(T).name
     g = lambda i, t: 0.05 * (i + 1) * (1 + t)
     h = step_fields(Ng, T, 70, tuple(slice(2, max(3, n // 2)) for n in Ng))
     U = (1.0,) + (0.0,) * (D - 1)
     runs = []
     for _ in range(2):
-        a = O.Flow(dims, U, T=T, nu=0.05, g=g, perdir=perdir)
+        a = O.Flow(dims, U, T=T, nu=0.05, g=g, perdir=perdir, dt=dt0)
         for k in ("u", "mu0", "mu1", "V"):
             getattr(a, k)[...] = h[k]
+        if p0 is not None:
+            a.p[...] = p0
         O.BC(a.u, U, False, perdir)
         O.BC(a.mu0, (0.0,) * D, False, perdir)
         O.BC(a.V, (0.0,) * D, False, perdir)
@@ -296,6 +293,23 @@ def test_mom_step_corrector_f_oracle_vs_xref(T, dims, perdir):
         assert np.array_equal(getattr(a, k), getattr(a2, k)), k
     assert b.n == b2.n and a.dt == a2.dt
     assert not np.array_equal(up, us)
+    return a, b, up, us, gc, dt
+
+
+STEP_CASES = [((20, 12, 8), ()), ((24, 16), ()), ((24, 16), (0,))]
+
+
+@pytest.mark.parametrize("T", TYPES)
+@pytest.mark.parametrize("dims,perdir", STEP_CASES)
+def test_mom_step_corrector_f_oracle_vs_xref(T, dims, perdir):
+    """After one mom_step! f holds the corrector's BDIM! value u_start + dt*(conv_diff(u') + g_corr) - V (Flow.jl:164-166,
+    :133), K = 12 (xref.mom_f).  u' is taken from the oracle's own operators replayed in mom_step!'s order, held
+    bit-identical to the oracle's step first.  Inputs: a non-uniform u, a body block with V != 0, a time-dependent body
+    force.  Controls: dt off by 64K eps, the samples shifted one plane, u_start replaced by u' must fail."""
+    D = len(dims)
+    Ng = tuple(n + 2 for n in dims)
+    tn = np.dtype(T).name
+    a, b, up, us, gc, dt = _oracle_step_and_twin(T, dims, perdir)
     C = X.host_cells({"u": up, "us": us, "V": a.V}, N=Ng)
     ins = np.all([(q >= 1) & (q <= n - 2) for q, n in zip(C.idx, Ng)], axis=0)
     for c in range(D):
@@ -350,6 +364,126 @@ def test_reductions_oracle_vs_xref(T):
     q = int(np.argmax(np.abs(a.astype(np.float64) * b).ravel(order="F")))
     drop = v - float(a.ravel(order="F")[q]) * float(b.ravel(order="F")[q])
     assert abs(got - drop) > 4 * np.log2(n) * X.eps(T) * M
+
+
+# ----------------------------------------------------------------------------- the projection half of mom_step!
+
+import xref_project as XP
+
+# extents (ghosts included): 3 and 4 -- one and two inside cells, where planes 0, 1, n-2 and n-1 coincide or touch -- in
+# every direction in turn, and non-cubic shapes
+BC_SHAPES = [(3, 6), (7, 3), (4, 5), (6, 4), (9, 7), (3, 5, 6), (6, 3, 5), (5, 6, 3), (4, 7, 5), (5, 4, 7), (7, 5, 4), (8, 6, 5)]
+
+
+def bc_neighbour(D, saveexit, perdir):
+    """a neighbouring (saveexit, perdir) setting whose BC! must differ: the exit flag where x is not periodic (it only
+    acts there), else x made a wall"""
+    return (not saveexit, perdir) if 0 not in perdir else (saveexit, tuple(j for j in perdir if j != 0))
+
+
+@pytest.mark.parametrize("T", TYPES)
+@pytest.mark.parametrize("Ng", BC_SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_BC_perBC_oracle_vs_xref(T, Ng):
+    """BC! and perBC! against the reference's plane loops replayed in xref.BC / xref.perBC, every cell, exactly: every
+    subset of periodic directions x saveexit; control: the neighbouring setting's result differs."""
+    D = len(Ng)
+    U = (1.0, 0.5, -0.25)[:D]
+    for q, perdir in enumerate([()] + periodic_subsets(D)):
+        h = field(Ng + (D,), T, "random", 2000 + q)
+        for saveexit in (False, True):
+            got = h.copy(order="F")
+            O.BC(got, U, saveexit, perdir)
+            assert np.array_equal(got, X.BC(h, U, saveexit, perdir)), (perdir, saveexit)
+            assert not np.array_equal(got, X.BC(h, U, *bc_neighbour(D, saveexit, perdir)))
+        if perdir:
+            s = field(Ng, T, "random", 2100 + q)
+            got = s.copy(order="F")
+            O.perBC(got, perdir)
+            assert np.array_equal(got, X.perBC(s, perdir)), perdir
+            assert not np.array_equal(got, X.perBC(s, perdir[1:]))
+
+
+@pytest.mark.parametrize("T", TYPES)
+@pytest.mark.parametrize("Ng", [(6, 3), (9, 10), (5, 3, 3), (7, 6, 5)], ids=lambda s: "x".join(map(str, s)))
+@pytest.mark.parametrize("kind", ["random", "ties", "scaled-up", "scaled-down"])
+def test_exitBC_oracle_vs_xref(T, Ng, kind):
+    """exitBC! against xref.exit_bc (K = 8) on one exit cell and on planes of 8 and 20, U and u0 of one scale; every other
+    cell untouched.  Controls: the imbalance correction left out, dt off by 64 K eps (random u0 on a plane)."""
+    D = len(Ng)
+    sc = {"scaled-up": 2.0 ** (20 if T == np.float32 else 60), "scaled-down": 2.0 ** -(20 if T == np.float32 else 60)}.get(kind, 1.0)
+    u0 = field(Ng + (D,), T, kind, 2200)
+    h = field(Ng + (D,), T, kind, 2201)
+    U1, dt = float(T(0.75 * sc)), float(T(0.3))
+    got = h.copy(order="F")
+    O.exitBC(got, u0, (U1, 0.0, 0.0), dt)
+    n = XP.check_exit(WORST, f"exit_bc {np.dtype(T).name}", T, got, u0, U1, dt, dt_control=kind == "random" and min(Ng[1:]) > 3)
+    assert n == int(np.prod([m - 2 for m in Ng[1:]]))
+    got[XP.exit_cells(Ng) + (0,)] = h[XP.exit_cells(Ng) + (0,)]
+    assert np.array_equal(got, h)
+
+
+# (inside extents, periodic directions): both solver types (the reference builds a MultiLevelPoisson on all but the second
+# and third), 2-D and 3-D, walls and periodic faces with L != 0 on them
+PROJECT_CASES = [((24, 16), ()), ((18, 11), ()), ((5, 9, 3), ()), ((16, 12, 12), ()), ((16, 12, 12), (1,)), ((16, 12, 12), (0, 2)),
+                 ((12, 12), (0, 1))]
+
+
+def _oracle_project_run(T, dims, perdir, kind, w, dt, seed=2300):
+    Ng = tuple(n + 2 for n in dims)
+    h = project_fields(Ng, T, kind, seed, body_block(Ng), perdir)
+    a, b = XP.oracle_flow(dims, T, h, perdir, dt)
+    n = XP.oracle_project(a, b, w)
+    p0 = XP.oracle_level0(b)
+    assert np.array_equal(p0.L, h["mu0"])
+    after = {"u": a.u.copy(order="F"), "p": a.p.copy(order="F"), "r": p0.r.copy(order="F")}
+    return h, n, after, p0.D.copy(order="F"), p0.iD.copy(order="F")      # (copies: the solver's arrays go with it)
+
+
+@pytest.mark.parametrize("T", TYPES)
+@pytest.mark.parametrize("dims,perdir", PROJECT_CASES)
+@pytest.mark.parametrize("w", [1.0, 0.5])
+def test_project_oracle_vs_xref(T, dims, perdir, w):
+    """project! with dt = 0.25 on random, tie-rich and step-front velocities (xref_inputs.project_fields): the velocity
+    correction (xref.correct, K = 4), the solve's invariant (xref.project_defect, K = 8 + 64 n), n <= 4 -- a condition on
+    the input --, the periodic ghost cells of p; the controls of xref_project.check_project.  Then with dt = 0.3: the
+    ghost cells of p in the non-periodic directions show the two scale passes alone (xref.scale_x, K = 2)."""
+    tn = np.dtype(T).name
+    ran = 0
+    for kind in ("random", "ties", "step"):
+        h, n, after, Dh, iDh = _oracle_project_run(T, dims, perdir, kind, w, 0.25)
+        assert 1 <= n <= 4, n
+        ran += XP.check_project(WORST, tn, T, perdir, w * 0.25, n, h, after, h["mu0"], Dh, iDh)
+    assert ran >= 2
+    if len(perdir) < len(dims):
+        h, n, after, _, _ = _oracle_project_run(T, dims, perdir, "random", w, 0.3)
+        dt = float(T(0.3))
+        changed = XP.check_scale(WORST, f"scale_x {tn}", "scale_x", T, perdir, h["p"], after["p"], dt)
+        assert changed > 0 or T == np.float64       # (the two roundings do move cells)
+
+
+@pytest.mark.parametrize("T", TYPES)
+@pytest.mark.parametrize("dims,perdir", STEP_CASES)
+def test_mom_step_u_oracle_vs_xref(T, dims, perdir):
+    """After one mom_step! with dt = 0.25 the inside cells hold 0.5*(u' + μddn(μ₁,f) + V + μ₀*f) - L*∂(0.125*p)
+    (xref.mom_u, K = 12: Flow.jl:166-167, :134, :142) with u' from the oracle's operators replayed in the step's order, held
+    bit-identical to the step, f as stored and p the final pressure.  Controls: dt off by 64 K eps, p shifted one plane,
+    u' replaced by u_start.  And BC! of the final u changes no bit of it."""
+    a, b, up, us, gc, dt = _oracle_step_and_twin(T, dims, perdir)
+    assert dt == 0.25 and max(b.n) <= 32
+    h = {"u": up, "f": a.f, "V": a.V, "mu0": a.mu0, "mu1": a.mu1, "L": a.mu0, "p": a.p, "got": a.u}
+    XP.check_mom_u(WORST, f"mom_u {np.dtype(T).name}", T, perdir, h, us, dt)
+    assert np.array_equal(X.BC(a.u, O.BCTuple(a.U, a.dt[:-1], a.D), False, perdir), a.u)
+
+
+@pytest.mark.parametrize("T", TYPES)
+@pytest.mark.parametrize("dims,perdir", STEP_CASES[:2])
+def test_mom_step_scale_chain_oracle_vs_xref(T, dims, perdir):
+    """The four scale passes of a whole step (*dt, /dt, *0.5dt, /0.5dt with dt = 0.3) on the ghost cells of p, which
+    nothing else writes: within 4 roundings of the start value (xref.scale_x, K = 4); control: p*dt fails."""
+    Ng = tuple(n + 2 for n in dims)
+    p0 = field(Ng, T, "random", 2400)
+    a, *_ = _oracle_step_and_twin(T, dims, perdir, dt0=0.3, p0=p0)
+    XP.check_scale(WORST, f"scale_x4 {np.dtype(T).name}", "scale_x4", T, perdir, p0, a.p, a.dt[0])
 
 
 def test_worst_ratios_are_recorded():

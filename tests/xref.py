@@ -44,7 +44,25 @@ K = {"conv_diff": 8, "div": 4, "bdim_f": 4, "bdim_u": 8, "flux_out": 4, "acceler
      "coarse_tail": 16,
      # r + A x = rhs on the level below Vcycle!'s: x and r take 8 updates (smoother, prolongate!+increment!, six pcg!
      # iterations), each rounds x, A*delta (mult: 4) and r; 8 * (1 + 4 + 1) = 48, rounded up to 64
-     "coarse_inv": 64}
+     "coarse_inv": 64,
+     # exitBC! (exit_bc below): v = u0 - (U*dt)*(u0 - u0[I-d1]) four roundings (U*dt, the difference, the product, the
+     # subtraction), the imbalance three (the sum's cast to T, the division, - U), the final subtraction one; the Float64 sum
+     # of n terms adds n*2^-53 of |v|, nothing at these sizes: about 2.5 eps M, K the 3-4x margin of the table
+     "exit_bc": 8,
+     # u - L*(x[I] - x[I-dc]) (correct below): three roundings, each at most eps/2 of M
+     "correct": 4,
+     # the velocity a whole mom_step! leaves (mom_u below): bdim_u 8 + correct 4, composed as mom_f is
+     "mom_u": 12,
+     # x .*= s; x ./= s (Flow.jl:139,144) on a cell nothing else writes: two roundings of |p|; the four passes of a whole
+     # step (*dt, /dt, *0.5dt, /0.5dt): four ("scale_x4")
+     "scale_x": 2, "scale_x4": 4}
+
+
+def K_project(n: int) -> int:
+    """K of project_defect after a solve of n solver! iterations: the initial residual 8 (K["residual"]), and per iteration
+    eight updates of x and r (Vcycle!'s smoother, prolongate!+increment!, six pcg! iterations) at 8 each, as derived next to
+    K["coarse_inv"]: 8 + 64 n"""
+    return 8 + 64 * int(n)
 
 
 def eps(T) -> float:
@@ -93,6 +111,70 @@ def host_cells(arrays: dict, idx=None, N=None, NA=None) -> Cells:
 def dl(d, D, k=1):
     """offset k along dimension d"""
     return tuple(k if q == d else 0 for q in range(D))
+
+
+# ------------------------------------------------------------------------------------------------ util.jl
+
+def _pl(N, q, j):
+    return tuple(q if d == j else slice(None) for d in range(len(N)))
+
+
+def BC(a: np.ndarray, A, saveexit=False, perdir=()):
+    """util.jl:192-210 BC!(a,A,saveexit,perdir) on a host vector field (N..., n): the reference's plane loops replayed in
+    their (i, j) order on a copy -- later loops read ghost cells that earlier ones wrote, so edges and corners hold what the
+    reference leaves there.  Pure copies and assignments (A[i] converted to the array's type): the result is exact."""
+    a = np.array(a, order="F", copy=True)
+    N, n = a.shape[:-1], a.shape[-1]
+    for i in range(n):
+        for j in range(n):
+            pl = lambda q: _pl(N, q, j) + (i,)
+            if j in perdir:
+                a[pl(0)] = a[pl(N[j] - 2)]                   # :196  a[I,i] = a[CIj(j,I,N[j]-1),i] over slice(N,1,j)
+                a[pl(N[j] - 1)] = a[pl(1)]                   # :197  a[I,i] = a[CIj(j,I,2),i] over slice(N,N[j],j)
+            elif i == j:
+                for q in (0, 1):                             # :200-202  Dirichlet on planes 1 and 2
+                    a[pl(q)] = A[i]
+                if not saveexit or i > 0:                    # :203  and on plane N unless the exit is saved
+                    a[pl(N[j] - 1)] = A[i]
+            else:
+                a[pl(0)] = a[pl(1)]                          # :205  a[I,i] = a[I+δ(j,I),i] over slice(N,1,j)
+                a[pl(N[j] - 1)] = a[pl(N[j] - 2)]            # :206  a[I,i] = a[I-δ(j,I),i] over slice(N,N[j],j)
+    return a
+
+
+def perBC(a: np.ndarray, perdir=()):
+    """util.jl:227-231 perBC!(a,perdir) on a host scalar field, the loops in perdir's order on a copy: exact."""
+    a = np.array(a, order="F", copy=True)
+    N = a.shape
+    for j in perdir:
+        a[_pl(N, 0, j)] = a[_pl(N, N[j] - 2, j)]            # :229
+        a[_pl(N, N[j] - 1, j)] = a[_pl(N, 1, j)]            # :230
+    return a
+
+
+def _sum_ld(v) -> np.longdouble:
+    """the sum of longdouble values, exact up to one rounding to longdouble: every value split into two float64 (its
+    64-bit significand fits), math.fsum for the leading float64, again for what that left"""
+    v = np.asarray(v, LD).ravel()
+    hi = v.astype(np.float64)
+    parts = np.concatenate([hi, (v - hi).astype(np.float64)]).tolist()
+    s0 = math.fsum(parts)
+    return LD(s0) + LD(math.fsum(parts + [-s0]))
+
+
+def exit_bc(C: Cells, U, dt, correction=True):
+    """util.jl:216-222 exitBC!(u,u⁰,U,Δt) at the exit cells C (0-based x index N1-1, every other index inside; ALL of
+    them: the imbalance is their mean): v = u⁰ - U*Δt*(u⁰ - u⁰[I-δ1]) (:219), ∮u = sum(v)/n - U (:220, the sum exact),
+    result v - ∮u (:221).  Reads "u0" (component 0); U = U[1].  M = M1 + mean(M1) + |mean v| + |U| with
+    M1 = |u⁰| + |U*Δt|*(|u⁰| + |u⁰[I-δ1]|).  correction=False leaves :220-221 out (the tests' control)."""
+    U, dt = LD(U), LD(dt)
+    a, b = C("u0", (), 0), C("u0", dl(0, C.D, -1), 0)
+    v = a - U * dt * (a - b)
+    M1 = abs(a) + abs(U * dt) * (abs(a) + abs(b))
+    n = len(C)
+    mean = _sum_ld(v) / n
+    M = M1 + _sum_ld(M1) / n + abs(mean) + abs(U)
+    return (v - (mean - U) if correction else v), M
 
 
 # ------------------------------------------------------------------------------------------------ Flow.jl
@@ -204,19 +286,26 @@ def bdim_f(C: Cells, c: int, dt, off=()):
     return u0 + dt * f - V, abs(u0) + abs(dt) * abs(f) + abs(V)
 
 
-def bdim_u(C: Cells, c: int, dt):
+def bdim_u(C: Cells, c: int, dt, stored=False):
     """Flow.jl:134 with μddn of Flow.jl:18-24: u += 0.5*sum_j μ₁[I,c,j]*(f[I+δj]-f[I-δj]) + V + μ₀*f, f from :133.
-    Inside cells only (inside_u(size(p)))."""
+    Inside cells only (inside_u(size(p))).  stored=True is :134 alone: "f" is read as the array holds it after :133, ghost
+    cells included, instead of being recomposed from u0 (dt is not used then)."""
     D = C.D
     s = np.zeros(len(C), LD)
     Ms = np.zeros(len(C), LD)
+
+    def f_at(off=()):
+        if not stored:
+            return bdim_f(C, c, dt, off)
+        v = C("f", off, c)
+        return v, abs(v)
     for j in range(D):
         m1 = C("mu1", (), c + D * j)
-        fp, Mp = bdim_f(C, c, dt, dl(j, D))
-        fm, Mm = bdim_f(C, c, dt, dl(j, D, -1))
+        fp, Mp = f_at(dl(j, D))
+        fm, Mm = f_at(dl(j, D, -1))
         s += m1 * (fp - fm)
         Ms += abs(m1) * (Mp + Mm)
-    f0, M0 = bdim_f(C, c, dt)
+    f0, M0 = f_at()
     u, V, mu0 = C("u", (), c), C("V", (), c), C("mu0", (), c)
     return u + LD(0.5) * s + V + mu0 * f0, abs(u) + LD(0.5) * Ms + abs(V) + abs(mu0) * M0
 
@@ -305,6 +394,75 @@ def jacobi_increment(C: Cells):
             AeM += abs(en) * abs(L)
     r, x = C("r"), C("x")
     return (e, eM), (r - Ae, abs(r) + AeM), (x + e, abs(x) + eM)
+
+
+# ------------------------------------------------------------------------------------------------ Flow.jl: project!, mom_step!
+
+def correct(C: Cells, c: int, x="x"):
+    """Flow.jl:142  u[I,c] -= L[I,c]*∂(c,I,x), ∂ of Flow.jl:2: x[I] - x[I-δc].  Reads "u" (before the loop), "L" and the
+    scalar `x` (the solver's solution, before `x ./= dt` of :144)."""
+    u, L = C("u", (), c), C("L", (), c)
+    a, b = C(x), C(x, dl(c, C.D, -1))
+    return u - L * (a - b), abs(u) + abs(L) * (abs(a) + abs(b))
+
+
+def dyadic(s) -> bool:
+    """s is a power of two: x * s and x / s are exact"""
+    return abs(math.frexp(float(s))[0]) == 0.5
+
+
+def mom_u(C: Cells, c: int, dt, w=0.5, planted=False):
+    """Flow.jl:166-167 with :134 and :142: the velocity one mom_step! leaves in the inside cells,
+        0.5*(u' + μddn(μ₁,f) + V + μ₀*f) - L*∂c(w*dt*p)
+    C reads "u" = u' (the predictor's projected velocity), the stored "f" (the corrector's :133 value, ghost cells
+    included), "V", "mu0", "mu1", "L" and "p" (the final pressure: project! solved for x = p*(w*dt) and divided it out
+    again, :144).  w*dt must be a power of two: then x = p*(w*dt) is the solver's x bit for bit.  The normal component on
+    its 0-based plane 1 is BC!'s (util.jl:200-202), not this: the caller leaves those cells out.  (planted=True lets a
+    control pass a dt that is off on purpose.)"""
+    s = LD(w) * LD(dt)
+    assert planted or dyadic(s), "mom_u: w*dt must be a power of two"
+    bv, bM = bdim_u(C, c, dt, stored=True)
+    L = C("L", (), c)
+    a, b = s * C("p"), s * C("p", dl(c, C.D, -1))
+    return LD(0.5) * bv - L * (a - b), LD(0.5) * bM + abs(L) * (abs(a) + abs(b))
+
+
+def scale_x(C: Cells, name="p"):
+    """Flow.jl:139,144  x .*= dt ... x ./= dt on a cell that nothing in between writes: the value it started with, within
+    one rounding per pass of M = |p| (K["scale_x"] for one project!, K["scale_x4"] for the two of a whole step)."""
+    p = C(name)
+    return p, abs(p)
+
+
+def project_shift(C: Cells, s, T):
+    """Poisson.jl:93-96 for the solve inside project! (Flow.jl:139-140): the mean that residual! subtracts from the initial
+    residual r0 = iD == 0 ? 0 : div(u) - A*(s*p), over C's cells (every inside cell); (shift, M) -- (0, M) when the mean is
+    within 4 eps of 0, where the reference may skip the shift (:95 tests 2 eps on the rounded mean).  C reads "u", "p" (the
+    pressure BEFORE project!), "L", "D", "iD"; s = w*dt."""
+    s = LD(s)
+    dv, dM = div(C)
+    Ax, AM = mult(C, "p")
+    live = C("iD") != 0
+    r0, rM = np.where(live, dv - s * Ax, LD(0)), np.where(live, dM + abs(s) * AM, LD(0))
+    n = len(C)
+    sh, shM = _sum_ld(r0) / n, _sum_ld(rM) / n
+    return (sh if abs(sh) > 4 * eps(T) else LD(0)), shM
+
+
+def project_defect(C: Cells, s, shift=0, shiftM=0):
+    """The invariant of solver! inside project! (Flow.jl:139-140): from r = z - A x - shift (Poisson.jl:93-96) every update
+    x += d, r -= A d (Jacobi!, increment!, pcg!) keeps r + A x = div(u) - shift, so at every inside cell
+        r_final + A*(s*p_after) - (div(u_before) - shift) = 0
+    in exact arithmetic, whatever the dot products that chose the d's summed to.  Returns (defect, M) with
+    M = M_div + shiftM + |s| * M_mult, the bound of the right-hand side and of A x; the check is |defect| <= K_project(n)
+    * eps * M.  C reads "r", "p" (after project!: x = p*s, exact as s must be a power of two), "u" (before project!), "L",
+    "D" and "iD" (where iD == 0 the residual started from 0 - shift, Poisson.jl:93, and the right-hand side is that)."""
+    s = LD(s)
+    assert dyadic(s), "project_defect: w*dt must be a power of two"
+    dv, dM = div(C)
+    Ax, AM = mult(C, "p")
+    live = C("iD") != 0
+    return C("r") + s * Ax - (np.where(live, dv, s * Ax) - LD(shift)), dM + LD(shiftM) + abs(s) * AM
 
 
 # ------------------------------------------------------------------------------------------------ MultiLevelPoisson.jl

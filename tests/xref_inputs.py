@@ -134,6 +134,48 @@ def step_fields(Ng, T, seed, block):
     return {k: np.asfortranarray(a.astype(T)) for k, a in (("u", u), ("mu0", mu0), ("mu1", mu1), ("V", V))}
 
 
+def project_scale(Ng) -> float:
+    """The velocity scale of project_fields: project!'s solver stops on the ABSOLUTE sum of r^2 over the grid (tol = 1e-4,
+    Poisson.jl:168, MultiLevelPoisson.jl:95), and on a long box the restarted six-step pcg! of a single level needs
+    hundreds of iterations to bring a residual down by a decade.  So the amplitude s (a power of two: scaling is exact)
+    keeps the START near the tolerance, n_cells * s^2 <= 2^-8: the oracle then needs 1 to 3 iterations on every case of
+    the project! checks (at n_cells * s^2 <= 2^-7 a single-level 18x11 grid takes 5).  Every check is relative to eps * M,
+    which scales with s."""
+    n = int(np.prod(Ng))
+    return 2.0 ** -int(np.ceil((8 + np.log2(n)) / 2))
+
+
+def body_block(Ng):
+    """The block of make_step (test_xref_step_gpu.py) for any extents: across the x seam at cell 64 where the grid reaches
+    it (else from mid-length), y from 2 to mid-height, every inside plane"""
+    x0 = min(58, max(1, Ng[0] // 2))
+    out = [slice(x0, max(x0 + 1, min(71, Ng[0] - 2))), slice(min(2, Ng[1] - 2), max(min(2, Ng[1] - 2) + 1, Ng[1] // 2 + 1))]
+    if len(Ng) == 3:
+        out.append(slice(1, Ng[2] - 1))
+    return tuple(out)
+
+
+def project_fields(Ng, T, kind, seed, block, perdir=()):
+    """Start of a project! check on a grid of extents Ng (ghosts included): a velocity of the given `kind` (field above:
+    random, ties, step, ...) times project_scale(Ng), the body of step_fields in `block` (mu0 is the solver's L: rows through
+    the block have varying coefficients, every other row is coefficient-uniform), a random start pressure p (ghost cells
+    included: the solver never writes the non-periodic ones), and BC! applied as mom_step! does before project!: u with
+    U = (scale, 0, ..), mu0 with 0 -- in a periodic direction the normal coefficient of planes 1, 2 and N stays 1."""
+    import xref as X
+    D = len(Ng)
+    s = project_scale(Ng)
+    h = step_fields(Ng, T, seed, block)
+    for c in perdir:
+        for q in (0, 1, Ng[c] - 1):
+            h["mu0"][tuple(q if d == c else slice(None) for d in range(D)) + (c,)] = 1
+    h["mu0"] = X.BC(h["mu0"], (0.0,) * D, False, perdir)
+    u = field(Ng + (D,), T, kind, seed + 1) * np.dtype(T).type(s)
+    h["u"] = X.BC(u, (s,) + (0.0,) * (D - 1), False, perdir)
+    h["p"] = X.perBC(field(Ng, T, "random", seed + 2) * np.dtype(T).type(s), perdir)
+    h["U"] = (s,) + (0.0,) * (D - 1)
+    return h
+
+
 def periodic_subsets(D):
     """every non-empty set of periodic directions of a D-dimensional grid"""
     return [p for n in range(1, D + 1) for p in itertools.combinations(range(D), n)]
