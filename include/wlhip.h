@@ -666,6 +666,61 @@ int wl_field_range(wl_dtype t, const wl_grid *g, const void *f, int kind, int ip
                    int absval, const int32_t lo[3], const int32_t hi[3], void *scratch_dev, int64_t scratch_bytes, double *out_dev);
 int wl_field_range_scratch(const wl_grid *g, int64_t *bytes);
 
+/* ------------------------------------------------------------------ two-point statistics (TwoPoint, waterlily_amd/twopoint.py)
+ * How the value at a cell relates to the value r cells further along one grid axis: for every separation r = 0 .. nsep - 1 the
+ * sums from which correlations, structure functions and the 1-D spectrum follow, over the cells lo_d <= J_d < hi_d (0-based, z
+ * global).  Both values of a pair are formed on the fly, as for wl_render_project, wl_downsample and wl_histogram (the same
+ * device function): no volume is filled first, and a line is read once for all its separations.
+ *   kinds : A = a, B = b, each WL_R_SCALAR, WL_R_UCOMP, WL_R_CENTRE or WL_R_METRIC + WL_M_* with ipar, par, par2 exactly as for
+ *           wl_render_project; the value is a double (an element is converted before the first operation, for Float32 and
+ *           Float64 alike).  WL_R_FACE is refused.  a->f and b->f may be different fields (a->f = p, b->f = u); both lie on the
+ *           grid g and have dtype t.  b == NULL: B is A, formed once per cell; the table has the bits of b = a given explicitly.
+ *   box   : lo == hi == NULL: inside().  0 <= lo_d < hi_d <= n_d - 1 (nzg - 1 along z); a metric kind's box (of either value)
+ *           must lie in inside().  D == 2: two entries are read.  A LINE is the box's cells along `axis` with the other indices
+ *           fixed: n = hi_axis - lo_axis cells, n <= WL_TP_MAX_LINE; 1 <= nsep <= n.
+ *   pairs : the partner of cell I at separation r is I' with axis index i + r.  periodic != 0: the index wraps inside the box,
+ *           lo + ((i - lo + r) mod n) -- no ghost cell is read for the wrap -- and every line has n pairs at every r.
+ *           periodic == 0: the pairs with i + r >= hi_axis do not exist; a line has n - r of them.
+ *   out   : out_dev[r * 10 + q], doubles.  With a = A(I), b = B(I'), d = b - a, d2 = d * d, every operation an IEEE double
+ *           operation rounded on its own (no FMA):
+ *             q = 0  N(r): the number of pairs, (lines) * (periodic ? n : n - r), formed by arithmetic, not accumulated
+ *             q = 1  sum a            q = 2  sum b            q = 3  sum a*a          q = 4  sum b*b        q = 5  sum a*b
+ *             q = 6  sum d2           q = 7  sum d2*d         q = 8  sum d2*d2        q = 9  sum fabs(d)*d2
+ *           Sums start at +0; NaN propagates into the rows and columns that read it (N(r) never).  accumulate == 0: the call
+ *           overwrites the 10 * nsep entries; accumulate != 0: the call's total, N(r) included, is added ONCE to the entry
+ *           that is there, old + new (a statistic over many steps).
+ *   order : fixed, and part of the contract.  Line q of the box (q = 0 .. lines - 1) is, for axis 0, the x-row j = lo_1 + q
+ *           mod e, k = lo_2 + q div e with e the box's y extent; for axis 1 (2) the line i = lo_0 + q mod e, k (j) = lo + q div e
+ *           with e the box's x extent.  L = 16 (n <= 255), 8 (n <= 511) or 4 lines make a ROUND; there are R = ceil(lines / L)
+ *           rounds and G = min(512, R) workgroups of 4 wavefronts; workgroup g takes the rounds g, g + G, ..., and of round t
+ *           wavefront w takes the lines t*L + w, t*L + w + 4, ... (below lines).  Wavefront v = 4*g + w adds, per separation
+ *           and column, the terms of its lines in that order -- ascending q -- and within a line by ascending i, into one
+ *           double that starts at +0.  The table's entry is the 4*G wavefront sums (the ones without a line are +0) added in
+ *           ascending v to a double that starts at +0.  No floating-point atomics anywhere; the same call gives the same bits.
+ *   slabs : axes 0 and 1 of a 3-D flow on z-slabs: a rank takes the lines in the planes it owns (the first rank of a ring
+ *           also takes the bottom ghost plane, as for wl_isosurface) with N(r) counting its own lines; a rank without a plane
+ *           in the box writes zeros (accumulate == 0).  The ranks' tables added in rank order (waterlily_amd.twopoint.combine)
+ *           are the statistic: column 0 is exact, the sums are the decomposed sums, not the undecomposed bits.  Nothing is
+ *           communicated.  A metric kind reads the first halo plane on each side, WL_R_CENTRE along z the one above, as for
+ *           wl_histogram.  Axis 2 on a z-slab is refused: the lines cross ranks and the halo is 2 planes.
+ * wl_twopoint_scratch: the bytes of scratch_dev for this grid (rank), axis, nsep and box: 4*G blocks of 9 * nsep doubles, host
+ * arithmetic (at 512^3 and nsep = 256: 38 MB).
+ * Refused with WL_E_ARG before the device is touched: NULL g, a, a->f, out_dev or scratch_dev, or b->f of a given b; an unknown
+ * t, kind or component; WL_R_FACE; axis outside 0..D-1; nsep outside 1..n; n > WL_TP_MAX_LINE; only one of lo and hi; a bad or
+ * empty box; a metric box outside inside(); scratch_bytes below wl_twopoint_scratch's; axis 2 on a z-slab.
+ * wl_twopoint_scratch: NULL g or bytes, a bad grid, and axis, nsep and box as above.  Asynchronous on the library's stream: two
+ * launches (the wavefront sums into scratch_dev, then one pass that adds them), nothing allocated.  WaterLily v1.3 has no such
+ * function to override. */
+#define WL_TP_MAX_LINE 1024   /* 4 lines x 2 values x 1024 doubles are the 64 KB of LDS a workgroup stages */
+typedef struct {
+    const void *f;            /* the field this value reads */
+    int32_t kind, ipar;
+    double par[3], par2[3];   /* of a metric kind (wl_metric); unused otherwise */
+} wl_tp_value;
+int wl_twopoint_scratch(const wl_grid *g, int axis, int nsep, const int32_t lo[3], const int32_t hi[3], int64_t *bytes);
+int wl_twopoint(wl_dtype t, const wl_grid *g, const wl_tp_value *a, const wl_tp_value *b, int axis, int nsep, int periodic,
+                const int32_t lo[3], const int32_t hi[3], int accumulate, void *scratch_dev, int64_t scratch_bytes, double *out_dev);
+
 /* ------------------------------------------------------------------ snapshots (VTK write / restart,ext/WaterLilyWriteVTKExt.jl:57-66,
  * ext/WaterLilyReadVTKExt.jl:28-45).  The reference copies whole fields to the host (`a.flow.u |> Array`) and permutes the vector
  * components to the front there (components_first, :79).  Here the field's LOCAL planes klo..khi are packed on the device into

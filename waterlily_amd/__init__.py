@@ -8,3 +8,5 @@ from .hist import Axis, Histogram  # noqa: F401
 from .mesh import MeshBody  # noqa: F401
 from .probes import Probes, Tracers, interp  # noqa: F401
 from .render import Renderer  # noqa: F401
+from . import twopoint  # noqa: F401
+from .twopoint import TwoPoint, Value  # noqa: F401

@@ -59,6 +59,11 @@ class HistAxis(C.Structure):
                 ("edges_dev", C.c_void_p)]
 
 
+class TpValue(C.Structure):
+    """wl_tp_value (include/wlhip.h): one of the two values of a two-point statistic"""
+    _fields_ = [("f", C.c_void_p), ("kind", C.c_int32), ("ipar", C.c_int32), ("par", C.c_double * 3), ("par2", C.c_double * 3)]
+
+
 WL_BODY_SPHERE, WL_BODY_TORUS, WL_BODY_PLATE, WL_BODY_CYLINDER = 0, 1, 2, 3
 WL_BODY_OP_UNION, WL_BODY_OP_MINUS, WL_BODY_OP_INTERSECT = 0, 1, 2
 WL_BODY_MAXLEAF = 6
@@ -239,6 +244,8 @@ def lib() -> C.CDLL:
         "wl_histogram": (i, [i, gp, vp, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), i, vp]),      # (a, b: byref(HistAxis))
         "wl_field_range": (i, [i, gp, vp, i, i, dp, dp, i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, i64, vp]),
         "wl_field_range_scratch": (i, [gp, C.POINTER(C.c_int64)]),
+        "wl_twopoint": (i, [i, gp, vp, vp, i, i, i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), i, vp, i64, vp]),      # (a, b: byref(TpValue))
+        "wl_twopoint_scratch": (i, [gp, i, i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
         "wl_snapshot_pack": (i, [i, gp, vp, i, i, i, i, vp]),
         "wl_snapshot_unpack": (i, [i, gp, vp, i, i, i, i, vp]),
         "wl_set_option": (i, [i, i]),

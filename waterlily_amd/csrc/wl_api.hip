@@ -23,6 +23,7 @@
 #include "wl_render.h"
 #include "wl_downsample.h"
 #include "wl_hist.h"
+#include "wl_twopoint.h"
 
 namespace wl {
 
@@ -1787,6 +1788,42 @@ int wl_field_range(wl_dtype t, const wl_grid *g, const void *f, int kind, int ip
     int l[3], h[3];
     WL_TRY(hist_box_args("wl_field_range", gg, D, kind >= WL_R_METRIC, lo, hi, l, h));
     WL_DISPATCH(t, D, (op_field_range<T, DD>(gg, &a, l, h, scratch_dev, out_dev)));
+}
+// the checks wl_twopoint and wl_twopoint_scratch share: axis, box -> l, h, the line's length and nsep
+static int twopoint_line_args(const char *who, const G &gg, int D, bool metric, int axis, int nsep, const int32_t lo[3], const int32_t hi[3], int l[3],
+                              int h[3]) {
+    if (axis < 0 || axis >= D) WL_BAD(who, "bad axis (0 <= axis < D)");
+    WL_TRY(hist_box_args(who, gg, D, metric, lo, hi, l, h));
+    const int n = h[axis] - l[axis];
+    if (n > TP_MAX_LINE) WL_BAD(who, "the box is longer than WL_TP_MAX_LINE = 1024 cells along axis");
+    if (nsep < 1 || nsep > n) WL_BAD(who, "bad nsep (1 <= nsep <= the box's extent along axis)");
+    if (axis == 2 && gg.dist) WL_BAD(who, "axis 2 on a z-slab: the lines cross ranks");
+    return 0;
+}
+int wl_twopoint_scratch(const wl_grid *g, int axis, int nsep, const int32_t lo[3], const int32_t hi[3], int64_t *bytes) {
+    if (!g || !bytes) return fail(WL_E_ARG, "wl_twopoint_scratch: null grid or bytes", __FILE__, __LINE__);
+    WL_TRY(check_grid(g));
+    const G gg = mkG(g);
+    int l[3], h[3];
+    WL_TRY(twopoint_line_args("wl_twopoint_scratch", gg, g->D, false, axis, nsep, lo, hi, l, h));
+    *bytes = tp_scratch_bytes(tp_box(gg, l, h, axis, nsep, 0));
+    return 0;
+}
+int wl_twopoint(wl_dtype t, const wl_grid *g, const wl_tp_value *a, const wl_tp_value *b, int axis, int nsep, int periodic, const int32_t lo[3],
+                const int32_t hi[3], int accumulate, void *scratch_dev, int64_t scratch_bytes, double *out_dev) {
+    if (!g || !a || !out_dev) return fail(WL_E_ARG, "wl_twopoint: null grid, value or table", __FILE__, __LINE__);
+    WL_TRY(check_grid(g));
+    WL_TRY(check_dtype("wl_twopoint", t));
+    if (!a->f || (b && !b->f)) return fail(WL_E_ARG, "wl_twopoint: null field of a value", __FILE__, __LINE__);
+    const int D = g->D;
+    WL_TRY(check_kind("wl_twopoint", a->kind, a->ipar, D, false));
+    if (b) WL_TRY(check_kind("wl_twopoint", b->kind, b->ipar, D, false));
+    const G gg = mkG(g);
+    int l[3], h[3];
+    WL_TRY(twopoint_line_args("wl_twopoint", gg, D, a->kind >= WL_R_METRIC || (b && b->kind >= WL_R_METRIC), axis, nsep, lo, hi, l, h));
+    if (!scratch_dev || scratch_bytes < tp_scratch_bytes(tp_box(gg, l, h, axis, nsep, periodic)))
+        return fail(WL_E_ARG, "wl_twopoint: no scratch, or fewer bytes than wl_twopoint_scratch asks for", __FILE__, __LINE__);
+    WL_DISPATCH(t, D, (op_twopoint<T, DD>(gg, a, b, axis, nsep, periodic, l, h, accumulate, scratch_dev, out_dev)));
 }
 int wl_tracer_advance(wl_dtype t, const wl_grid *g, const void *u, double *x_dev, int64_t m, double dt, int perdir_mask) {
     WL_TRY(check_grid(g));
