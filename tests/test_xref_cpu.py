@@ -7,7 +7,9 @@ import pytest
 
 import xref as X
 from oracle import wl_oracle as O
-from xref_inputs import KINDS, body_block, coefficients, field, periodic_subsets, project_fields, step_fields
+from xref_inputs import (KINDS, body_block, coefficients, field, pcg_body, pcg_cases, pcg_chains, pcg_wave, periodic_subsets,
+                         project_fields, step_fields)
+from xref_pcg import replay
 
 TYPES = [np.float32, np.float64]
 K = X.K
@@ -186,6 +188,63 @@ def test_pcg_one_iteration_and_exits_oracle_vs_xref(T, Ng):
     (al2, _), *_ = X.pcg1_ref(L, p.D.copy(order="F"), p.iD.copy(order="F"), np.asfortranarray(r2))
     assert abs(al2) > 1e2
     assert O.pcg(p, it=1) == 0 and np.array_equal(p.x, x) and np.array_equal(p.r, r2)
+
+
+def oracle_replay(inp, T, key, kmax=6):
+    """xref_pcg.replay on the CPU oracle: every run starts from inp's x0, r0 and z (eps zeroed: its ghost cells too)"""
+    p = O.Poisson(inp["x0"].copy(order="F"), inp["L"].copy(order="F"), inp["z"].copy(order="F"), perdir=inp["perdir"])
+
+    def run(k):
+        p.x[...], p.r[...], p.z[...], p.eps[...] = inp["x0"], inp["r0"], inp["z"], 0
+        n = O.pcg(p, it=k)
+        return n, p.x.copy(order="F"), p.r.copy(order="F"), p.eps.copy(order="F")
+    return replay(run, inp, p.D.copy(order="F"), p.iD.copy(order="F"), T, kmax, WORST, key)
+
+
+PCG_BODY = [((10, 9), "body", None, ()), ((9, 8, 7), "body", None, ()), ((6, 5, 3), "body", None, ()),
+            ((12, 7, 6), "row", "f1", ()), ((12, 7, 6), "row", "y", ()),
+            ((10, 7, 6), "body", None, (0,)), ((10, 7, 6), "body", None, (1, 2)), ((10, 7, 6), "body", None, (0, 1, 2)),
+            ((14, 9), "body", None, (1,))]
+
+
+@pytest.mark.parametrize("T", TYPES)
+@pytest.mark.parametrize("Ng,Lkind,edge,perdir", PCG_BODY)
+def test_pcg_every_iteration_oracle_vs_xref(T, Ng, Lkind, edge, perdir):
+    """pcg!(it=k), k = 1..6, from a random x0 with bodies, row cases and periodic directions (z uploaded with ghost values of
+    order 1: the shell term of z.eps): eps_k (K = 8), x_k and r_k (K = 16) of every iteration against the replay of that
+    iteration alone, n, the controls of xref_pcg.replay; no exit on these inputs"""
+    out = oracle_replay(pcg_body(Ng, T, 40, Lkind, edge, seam=3, perdir=perdir), T, f"pcg6 {np.dtype(T).name} ")
+    assert out["exit"] is None and out["n"] == [1, 2, 3, 4, 5, 6]
+
+
+@pytest.mark.parametrize("T", TYPES)
+@pytest.mark.parametrize("Ng,axis", [((10, 8, 5), 1), ((6, 5, 9), 2), ((9, 11), 1)])
+def test_pcg_chains_leave_after_two_updates_oracle_vs_xref(T, Ng, axis):
+    """the `chains` inputs: two updates, then :138 in iteration 2 for every it >= 2; x keeps the second update"""
+    out = oracle_replay(pcg_chains(Ng, T, 41, axis), T, f"pcg6 {np.dtype(T).name} ")
+    assert out["exit"] == (":138", 2) and out["n"] == [1, 2, 2, 2, 2, 2]
+
+
+@pytest.mark.parametrize("T", TYPES)
+@pytest.mark.parametrize("Ng", [(34, 6, 5), (66, 4, 3), (34, 5)])
+def test_pcg_wave_leaves_at_alpha_oracle_vs_xref(T, Ng):
+    """the `wave` inputs: one update, then :132 (alpha_2 about 156) in iteration 2 for every it >= 2; eps is the new direction"""
+    out = oracle_replay(pcg_wave(Ng, T), T, f"pcg6 {np.dtype(T).name} ")
+    assert out["exit"] == (":132", 2) and out["n"] == [1, 1, 1, 1, 1, 1]
+
+
+@pytest.mark.parametrize("q", [q for q, c in enumerate(pcg_cases(np.float32)) if c["group"] != "tall"])
+def test_pcg_kernel_cases_oracle_vs_xref(q):
+    """the inputs the kernels are held to (xref_inputs.pcg_cases: the dispatch-edge shapes) through the oracle: the same
+    checks, and with them the branch margins and the exits of every case, on a machine without a GPU.  Float32 only, and
+    without the 4096-row planes: the oracle's dot is ONE sequential double sum, and in Float64 that sum's own rounding
+    grows with the number of cells (eps_k: 6.5 eps*M at 1100 cells, 8.4 at 5544), which K["pcg_eps"] does not count --
+    the kernels sum in a tree; test_pcg_every_iteration_oracle_vs_xref holds the Float64 oracle at the small sizes."""
+    T = np.float32
+    case = pcg_cases(T)[q]
+    out = oracle_replay(case["make"](), T, f"pcg6 {np.dtype(T).name} ")
+    want = {"chains": ((":138", 2), [1, 2, 2, 2, 2, 2]), "wave": ((":132", 2), [1] * 6)}.get(case["group"], (None, [1, 2, 3, 4, 5, 6]))
+    assert (out["exit"], out["n"]) == want
 
 
 @pytest.mark.parametrize("T", TYPES)

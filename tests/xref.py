@@ -55,7 +55,14 @@ K = {"conv_diff": 8, "div": 4, "bdim_f": 4, "bdim_u": 8, "flux_out": 4, "acceler
      "mom_u": 12,
      # x .*= s; x ./= s (Flow.jl:139,144) on a cell nothing else writes: two roundings of |p|; the four passes of a whole
      # step (*dt, /dt, *0.5dt, /0.5dt): four ("scale_x4")
-     "scale_x": 2, "scale_x4": 4}
+     "scale_x": 2, "scale_x4": 4,
+     # the search direction of pcg! iteration k >= 2 (pcg_step_ref below), eps = beta*eps + r*iD with beta = rho1/rho0 in T:
+     # six roundings -- rho1 and rho0 to T, the T division, z' = r*iD, beta*eps, the sum -- each counted as a whole eps of
+     # M = |beta*eps| + |r*iD| (rho's terms r*(r*iD) share iD's sign, so the roundings of z' inside the sums, eps/2 of rho
+     # each, fit into the halves left over): 6, rounded up to 8.  (Float32 sums rho in double; a Float64 sum rounds as it
+     # goes, which the count leaves out: the kernels' tree sums stay well inside, the oracle's one sequential sum does so
+     # up to about a thousand cells -- DESIGN.md has the figures)
+     "pcg_eps": 8}
 
 
 def K_project(n: int) -> int:
@@ -589,6 +596,90 @@ def pcg1_ref(L, D, iD, r):
     x1 = (alpha * ef, abs(alpha) * eM.ravel(order="F") + Ma * abs(ef))
     r1 = (rf - alpha * zv, abs(rf) + abs(alpha) * zM + Ma * abs(zv))
     return (alpha, Ma), (ef, eM.ravel(order="F")), (zv, zM), x1, r1, ins
+
+
+def pcg_step_ref(L, D, iD, z_up, perdir, x, r, e_prev, r_pp, e_k, T, shell=True):
+    """Iteration k of pcg! (Poisson.jl:123-143) replayed on its own from stored T values.  pcg! keeps nothing between
+    calls and a call of it=k leaves x_k, r_k and eps_k (the last iteration skips :140, so eps_k is the direction iteration
+    k used): x = x_{k-1}, r = r_{k-1}, e_prev = eps_{k-1} are the arrays a call of it=k-1 left, r_pp = r_{k-2} those of
+    it=k-2 (the start for k = 2), e_k the STORED direction of the call of it=k; k = 1: e_prev = r_pp = None.  z_up is the
+    z array as uploaded: pcg! writes z inside only, and z.eps is a whole-array dot (:131), so in the ghost planes that
+    perBC! fills with eps (:129) the uploaded z counts (shell=False leaves those cells out: the tests' control).
+
+    Returns a dict of (value, M) pairs in longdouble, whole arrays flattened in Fortran order, scalars as 0-d:
+      rho    rho_{k-1} = sum r*(r*iD) (:126,137), M = 2 sum |r*(r*iD)| as in pcg1_ref
+      beta   rho_{k-1}/rho_{k-2} (:139; k >= 2)
+      eps    beta*eps_{k-1} + r*iD (:140; k = 1: r*iD, :125), M = c*|beta*eps| + |r*iD| with c = 1 when rho's terms share
+             a sign (K["pcg_eps"])
+      alpha  rho_{k-1}/(z.eps_k) (:131), z = A eps_k inside from mult on perBC(e_k), the uploaded z in the ghost cells
+             (K["alpha"])
+      x, r   x + alpha*eps_k and r - alpha*A eps_k (:133), M as in pcg1_ref: alpha's own bound enters (K["pcg"])
+    and "branch": the scalars pcg! branches on as (name, |value|, threshold, bound) -- |rho| against 10 eps_T (:127 for
+    k = 1, :138 of iteration k-1 else), |alpha| against 1e-2 and 1e2 (:132); "exit": None when iteration k updates x and
+    r, else ":127" / ":138" (no iteration k: n = k-1 updates were made) or ":132" (eps_k is the new direction, x and r
+    stay: n = k-1); "ins": the mask of inside cells; "Aeps" = (A eps_k, M) with zeros outside, "_eps_k" and "_eps_prev" the
+    two directions in longdouble (pcg_step_planted builds the controls from them)."""
+    Ng = r.shape
+    e = LD(eps(T))
+    flat = lambda a: np.asarray(a, LD).ravel(order="F")
+    rf, idf, xf = flat(r), flat(iD), flat(x)
+    zp = rf * idf                                                     # z' = r*iD (:125,136)
+    rho, Mrho = _sum_ld(rf * zp), 2 * _sum_ld(abs(rf * zp))
+    out = {"rho": (rho, Mrho), "branch": [("rho", abs(rho), LD(10) * e, e * Mrho)], "exit": None}
+    C = host_cells({"L": L, "D": D, "e": perBC(e_k, perdir)}, N=Ng)
+    ins = np.all([(q >= 1) & (q <= n - 2) for q, n in zip(C.idx, Ng)], axis=0)
+    out["ins"] = ins
+    if abs(rho) < LD(10) * e:
+        out["exit"] = ":127" if e_prev is None else ":138"
+        return out
+    if e_prev is None:
+        out["eps"] = (zp, abs(zp))
+    else:
+        rp = flat(r_pp)
+        tp = rp * (rp * idf)
+        rho0, Mrho0 = _sum_ld(tp), 2 * _sum_ld(abs(tp))
+        beta = rho / rho0
+        c = (Mrho / abs(rho) + Mrho0 / abs(rho0)) / 4
+        out["beta"] = (beta, c * abs(beta))
+        ep = flat(e_prev)
+        out["_eps_prev"] = ep
+        out["eps"] = (beta * ep + zp, c * abs(beta * ep) + abs(zp))
+    zv, zM = mult(C, "e")
+    zg = flat(z_up) if shell else np.zeros(len(ins), LD)
+    zv, zM = np.where(ins, zv, 0), np.where(ins, zM, 0)
+    ef = C("e")
+    ze = _sum_ld(np.where(ins, zv, zg) * ef)
+    Mze = 2 * _sum_ld(np.where(ins, zM, abs(zg)) * abs(ef))
+    alpha = rho / ze
+    Ma = abs(alpha) * (Mrho / abs(rho) + Mze / abs(ze))
+    out["alpha"] = (alpha, Ma)
+    out["Aeps"] = (zv, zM)
+    out["_eps_k"] = ef
+    out["branch"] += [("alpha_lo", abs(alpha), LD(1e-2), K["alpha"] * e * Ma), ("alpha_hi", abs(alpha), LD(1e2), K["alpha"] * e * Ma)]
+    if abs(alpha) < 1e-2 or abs(alpha) > 1e2:
+        out["exit"] = ":132"
+        return out
+    out["x"] = (xf + alpha * ef, abs(xf) + abs(alpha) * abs(ef) + Ma * abs(ef))
+    out["r"] = (rf - alpha * zv, abs(rf) + abs(alpha) * zM + Ma * abs(zv))
+    return out
+
+
+def pcg_step_planted(ref, what, T):
+    """`ref` (of pcg_step_ref) with one planted error, for the tests' controls: what = "alpha": alpha off by
+    64 K eps M_alpha/|alpha| relative, x and r recomputed with it; "beta": beta off likewise, eps recomputed."""
+    out = dict(ref)
+    e = LD(eps(T))
+    if what == "alpha":
+        (a, Ma), (xv, xM), (rv, rM), (zv, _) = ref["alpha"], ref["x"], ref["r"], ref["Aeps"]
+        d = a * 64 * K["alpha"] * e * (Ma / abs(a))
+        # x = x0 + alpha*eps, r = r0 - alpha*A eps: the planted alpha moves them by d*eps and -d*A eps
+        out["x"] = (xv + d * ref["_eps_k"], xM)
+        out["r"] = (rv - d * zv, rM)
+    else:
+        (b, Mb), (ev, eM) = ref["beta"], ref["eps"]
+        d = b * 64 * K["pcg_eps"] * e * (Mb / abs(b))
+        out["eps"] = (ev + d * ref["_eps_prev"], eM)
+    return out
 
 
 # ------------------------------------------------------------------------------------------------ reductions

@@ -176,6 +176,128 @@ def project_fields(Ng, T, kind, seed, block, perdir=()):
     return h
 
 
+# ------------------------------------------------------------------------------------------------ pcg! replay inputs
+# Each returns a dict of host arrays on a grid of extents Ng (ghosts included): L, the start x0 and r0 (ghost cells of r
+# are 0: outside(p.r) ≡ 0, Poisson.jl:146), the z to upload, and "perdir".
+
+def _zero_ghosts(a):
+    for d in range(a.ndim):
+        ix = [slice(None)] * a.ndim
+        ix[d] = [0, a.shape[d] - 1]
+        a[tuple(ix)] = 0
+    return a
+
+
+def pcg_body(Ng, T, seed, kind="body", edge=None, seam=64, perdir=(), solid=True):
+    """`coefficients` bodies and row cases, a random x0 (not zero), a random r, a random z of order 1 everywhere (pcg! never
+    reads what is uploaded inside; the ghost cells count where perBC! fills eps).  With periodic directions L is
+    BC!(L, 0, false, perdir) of the random field with its solid block: a periodic operator, coupled across the seam.
+    solid=False (grids of a handful of cells, where pcg! converges within the six iterations): no solid block, so the cells
+    are one connected set, and the mean of r over them is removed -- r then has no component along the constant vector, on
+    which A eps = 0 and alpha = rho/(z.eps) is a quotient of two rounding errors that no bound could place."""
+    import xref as X
+    D = len(Ng)
+    if not solid:
+        rng = np.random.default_rng(seed)
+        L = np.asfortranarray((0.2 + 0.8 * rng.random(Ng + (D,))).astype(T))
+        L = X.BC(L, (0.0,) * D, False, ())
+        r = _zero_ghosts(field(Ng, T, "random", seed + 2))
+        ins = tuple(slice(1, n - 1) for n in Ng)
+        r[ins] -= np.dtype(T).type(r[ins].astype(np.float64).mean())
+        return {"L": L, "x0": field(Ng, T, "random", seed + 1), "r0": r, "z": field(Ng, T, "random", seed + 3), "perdir": ()}
+    if perdir:
+        rng = np.random.default_rng(seed)
+        L = np.asfortranarray((0.2 + 0.8 * rng.random(Ng + (D,))).astype(T))
+        L[tuple(slice(max(1, n // 3), max(2, n // 3 + 2)) for n in Ng)] = 0
+        L = X.BC(L, (0.0,) * D, False, perdir)
+    else:
+        L = coefficients(Ng, T, seed, kind, edge, seam)
+    return {"L": L, "x0": field(Ng, T, "random", seed + 1), "r0": _zero_ghosts(field(Ng, T, "random", seed + 2)),
+            "z": field(Ng, T, "random", seed + 3), "perdir": tuple(perdir)}
+
+
+def pcg_chains(Ng, T, seed, axis=1):
+    """L is non-zero only on the `axis` faces inside disjoint triples of cells (inside indices 1-3, 4-6, ... along `axis`,
+    in every line of cells), with random dyadic coefficients k/8, k = 2..8; r is dyadic (multiples of 1/16) and sums to
+    zero over each triple; x0 is dyadic too.  A triple is a weighted path of three vertices, whose Jacobi-preconditioned
+    operator has the eigenvalues {0, 1, 2} whatever the weights, and r has no component along the null vector: pcg! makes
+    exactly two updates, after which r is zero up to rounding, and leaves through :138 in iteration 2.  Cells outside the
+    triples have D = 0, iD = 0 and r = 0."""
+    D = len(Ng)
+    rng = np.random.default_rng(seed)
+    L = np.zeros(Ng + (D,), T, order="F")
+    r = np.zeros(Ng, T, order="F")
+    nt = (Ng[axis] - 2) // 3
+    assert nt >= 1, "chains need three inside cells along the axis"
+    other = tuple(n - 2 for d, n in enumerate(Ng) if d != axis)
+    for t in range(nt):
+        a = 1 + 3 * t
+        at = lambda q: tuple(q if d == axis else slice(1, n - 1) for d, n in enumerate(Ng))
+        for f in (a + 1, a + 2):                              # the face between cells f-1 and f belongs to cell f
+            L[at(f) + (axis,)] = rng.integers(2, 9, size=other) / 8.0
+        ra, rb = (rng.integers(-8, 9, size=other) / 16.0 for _ in range(2))
+        ra = np.where((ra == 0) & (rb == 0), 0.5, ra)
+        r[at(a)], r[at(a + 1)], r[at(a + 2)] = ra, rb, -(ra + rb)
+    x0 = np.asfortranarray((rng.integers(-8, 9, size=Ng) / 8.0).astype(T))
+    return {"L": L, "x0": x0, "r0": r, "z": field(Ng, T, "random", seed + 3), "perdir": ()}
+
+
+def pcg_wave(Ng, T):
+    """A fully periodic box with unit coefficients and r = cos(2π 8i/n) + 0.01 cos(2π i/n) over the n = Ng[0] - 2 inside
+    cells of x (n = 32: waves 4 and 32 cells long), constant in the other directions; z and x0 are zero.  The first
+    iteration removes the short wave (alpha_1 = 3 in 3-D: A has the eigenvalue -2 there, iD = -1/6); the second direction
+    is the long wave, whose Rayleigh quotient is 0.0064, so alpha_2 is about 156 > 100: pcg! leaves through :132 in
+    iteration 2 after one update."""
+    D = len(Ng)
+    n = Ng[0] - 2
+    i = np.arange(n)
+    w = np.cos(2 * np.pi * (n // 4) * i / n) + 0.01 * np.cos(2 * np.pi * i / n)
+    r = np.zeros(Ng, T, order="F")
+    r[tuple(slice(1, m - 1) for m in Ng)] = w.reshape((n,) + (1,) * (D - 1)).astype(T)
+    zero = np.zeros(Ng, T, order="F")
+    return {"L": np.ones(Ng + (D,), T, order="F"), "x0": zero.copy(order="F"), "r0": r, "z": zero, "perdir": tuple(range(D))}
+
+
+def pcg_cases(T):
+    """The cases of the per-iteration pcg! checks on the kernels (test_xref_pcg_gpu.py; test_xref_cpu.py runs the oracle
+    through the same inputs, the 4096-row ones excepted, so that their branch margins are checked without a GPU): dicts of
+    id, group, dims (interior extents) and make() -> the inputs.  V = 4 (Float32) / 2 (Float64) cells per 16-B vector.
+      first   x = V, V+1 (no vector kernels: scalar, finalize launches), 63V, 64V, 65V; y = 3..9; z = 2..6
+      small   (V-1, 5, 1) (five cells in Float64: pcg! converges and leaves, see pcg_body's solid=False) and 2-D: scalar
+              kernels, one plane
+      long    (V, 4, 40): 320 partials, more than one pass of a 256-thread sum; (V, 4, 131): the cap of 128 z chunks binds
+      tall    (V, 4096, 3): the largest plane of the in-kernel sums (1024 workgroups, one chunk); (V, 4100, 3): the first
+              that falls back to the finalize launches on a vector level (1032)
+      rows    (65V, 5, 4) uniform except one coefficient at the first face, the x seam and the last face of a row
+      chains  x = 64V and 65V with triples along y, x = 65V with triples along z
+      wave    32 cells in x
+      periodic  body coefficients with perdir (0,), (1, 2) and (0, 1, 2), z uploaded with ghost values of order 1; extents at
+              which the shell sum's partials (blocks of 256 cells of the largest plane, per plane) are no multiple of 8"""
+    v = 4 if np.dtype(T) == np.float32 else 2
+    out = []
+
+    def add(group, dims, make):
+        q = len(out)
+        out.append({"id": f"{group}-{'x'.join(map(str, dims))}-{q}", "group": group, "dims": tuple(dims),
+                    "make": (lambda: make(tuple(n + 2 for n in dims), 700 + 10 * q))})
+    for s in [(v, 4, 2), (v + 1, 9, 3), (63 * v, 8, 5), (64 * v, 3, 6), (65 * v, 5, 5)]:
+        add("first", s, lambda Ng, sd: pcg_body(Ng, T, sd))
+    add("small", (v - 1, 5, 1), lambda Ng, sd: pcg_body(Ng, T, sd, solid=False))
+    add("small", (7, 6), lambda Ng, sd: pcg_body(Ng, T, sd))
+    for s in [(v, 4, 40), (v, 4, 131)]:
+        add("long", s, lambda Ng, sd: pcg_body(Ng, T, sd))
+    for s in [(v, 4096, 3), (v, 4100, 3)]:
+        add("tall", s, lambda Ng, sd: pcg_body(Ng, T, sd))
+    for edge in ("f1", "seam", "n-1"):
+        add("rows", (65 * v, 5, 4), lambda Ng, sd, edge=edge: pcg_body(Ng, T, sd, "row", edge, seam=64 * v))
+    for s, ax in [((64 * v, 6, 3), 1), ((65 * v, 7, 4), 1), ((65 * v, 4, 6), 2)]:
+        add("chains", s, lambda Ng, sd, ax=ax: pcg_chains(Ng, T, sd, ax))
+    add("wave", (32, 4, 3), lambda Ng, sd: pcg_wave(Ng, T))
+    for s, per in [((65 * v, 3, 3), (0,)), ((3 * v, 6, 5), (1, 2)), ((65 * v, 3, 3), (0, 1, 2)), ((3 * v, 6, 5), (0, 1, 2))]:
+        add("periodic", s, lambda Ng, sd, per=per: pcg_body(Ng, T, sd, perdir=per))
+    return out
+
+
 def periodic_subsets(D):
     """every non-empty set of periodic directions of a D-dimensional grid"""
     return [p for n in range(1, D + 1) for p in itertools.combinations(range(D), n)]
