@@ -54,7 +54,7 @@ def short(d):
         m = re.match(r"(?:float|double), (true|false), (true|false), (\d+)", args)
         if m:
             extra = [f"fuse={m.group(1)}", f"copy={m.group(2)}", f"BY={m.group(3)}"]
-    elif kern in ("k_hist", "k_field_range", "k_twopoint"):
+    elif kern in ("k_hist", "k_field_range", "k_twopoint", "k_rg_init", "k_rg_table", "k_rg_peak"):
         m = re.match(r"(?:float|double), (\d), (true|false)(?:, (\d))?", args)
         if m:
             extra = [f"D={m.group(1)}", f"metric={m.group(2)}"] + ([f"B={('none', 'plain', 'metric')[int(m.group(3))]}"] if m.group(3) else [])

@@ -7,6 +7,8 @@ from . import hist  # noqa: F401
 from .hist import Axis, Histogram  # noqa: F401
 from .mesh import MeshBody  # noqa: F401
 from .probes import Probes, Tracers, interp  # noqa: F401
+from . import regions  # noqa: F401
+from .regions import Regions, RegionSeries  # noqa: F401
 from .render import Renderer  # noqa: F401
 from . import twopoint  # noqa: F401
 from .twopoint import TwoPoint, Value  # noqa: F401

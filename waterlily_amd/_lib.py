@@ -64,6 +64,15 @@ class TpValue(C.Structure):
     _fields_ = [("f", C.c_void_p), ("kind", C.c_int32), ("ipar", C.c_int32), ("par", C.c_double * 3), ("par2", C.c_double * 3)]
 
 
+class RgValue(C.Structure):
+    """wl_rg_value (include/wlhip.h): the value whose threshold set wl_regions labels"""
+    _fields_ = [("f", C.c_void_p), ("kind", C.c_int32), ("ipar", C.c_int32), ("par", C.c_double * 3), ("par2", C.c_double * 3),
+                ("absval", C.c_int32)]
+
+
+WL_RG_BELOW, WL_RG_ABOVE = 0, 1
+
+
 WL_BODY_SPHERE, WL_BODY_TORUS, WL_BODY_PLATE, WL_BODY_CYLINDER = 0, 1, 2, 3
 WL_BODY_OP_UNION, WL_BODY_OP_MINUS, WL_BODY_OP_INTERSECT = 0, 1, 2
 WL_BODY_MAXLEAF = 6
@@ -246,6 +255,8 @@ def lib() -> C.CDLL:
         "wl_field_range_scratch": (i, [gp, C.POINTER(C.c_int64)]),
         "wl_twopoint": (i, [i, gp, vp, vp, i, i, i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), i, vp, i64, vp]),      # (a, b: byref(TpValue))
         "wl_twopoint_scratch": (i, [gp, i, i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+        "wl_regions": (i, [i, gp, vp, i, d, i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, i64, vp, vp, vp, vp, i64]),      # (v: byref(RgValue))
+        "wl_regions_scratch": (i, [gp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
         "wl_snapshot_pack": (i, [i, gp, vp, i, i, i, i, vp]),
         "wl_snapshot_unpack": (i, [i, gp, vp, i, i, i, i, vp]),
         "wl_set_option": (i, [i, i]),

@@ -24,6 +24,7 @@
 #include "wl_downsample.h"
 #include "wl_hist.h"
 #include "wl_twopoint.h"
+#include "wl_regions.h"
 
 namespace wl {
 
@@ -1824,6 +1825,46 @@ int wl_twopoint(wl_dtype t, const wl_grid *g, const wl_tp_value *a, const wl_tp_
     if (!scratch_dev || scratch_bytes < tp_scratch_bytes(tp_box(gg, l, h, axis, nsep, periodic)))
         return fail(WL_E_ARG, "wl_twopoint: no scratch, or fewer bytes than wl_twopoint_scratch asks for", __FILE__, __LINE__);
     WL_DISPATCH(t, D, (op_twopoint<T, DD>(gg, a, b, axis, nsep, periodic, l, h, accumulate, scratch_dev, out_dev)));
+}
+// the checks wl_regions and wl_regions_scratch share: one rank, box -> l, h, fewer than 2^31 cells
+static int regions_box_args(const char *who, const G &gg, int D, bool metric, const int32_t lo[3], const int32_t hi[3], int l[3], int h[3]) {
+    if (gg.dist) WL_BAD(who, "a decomposed flow (z-slabs): regions cross ranks");
+    WL_TRY(hist_box_args(who, gg, D, metric, lo, hi, l, h));
+    if ((int64_t)(h[0] - l[0]) * (h[1] - l[1]) * (h[2] - l[2]) >= (int64_t)1 << 31) WL_BAD(who, "the box holds 2^31 cells or more");
+    return 0;
+}
+int wl_regions_scratch(const wl_grid *g, const int32_t lo[3], const int32_t hi[3], int64_t *bytes) {
+    if (!g || !bytes) return fail(WL_E_ARG, "wl_regions_scratch: null grid or bytes", __FILE__, __LINE__);
+    WL_TRY(check_grid(g));
+    const G gg = mkG(g);
+    int l[3], h[3];
+    WL_TRY(regions_box_args("wl_regions_scratch", gg, g->D, false, lo, hi, l, h));
+    *bytes = rg_scratch_bytes((long)(h[1] - l[1]) * (h[2] - l[2]));
+    return 0;
+}
+int wl_regions(wl_dtype t, const wl_grid *g, const wl_rg_value *v, int cmp, double c, int periodic_mask, const int32_t lo[3],
+               const int32_t hi[3], int32_t *label_dev, int64_t cap, int64_t *tab_dev, double *ext_dev, int64_t *n_dev, void *scratch_dev,
+               int64_t scratch_bytes) {
+    if (!g || !v || !label_dev || !n_dev || !scratch_dev) return fail(WL_E_ARG, "wl_regions: null grid, value, labels, counts or scratch", __FILE__, __LINE__);
+    WL_TRY(check_grid(g));
+    WL_TRY(check_dtype("wl_regions", t));
+    if (!v->f) return fail(WL_E_ARG, "wl_regions: null field of the value", __FILE__, __LINE__);
+    const int D = g->D;
+    WL_TRY(check_kind("wl_regions", v->kind, v->ipar, D, false));
+    if (cmp != WL_RG_BELOW && cmp != WL_RG_ABOVE) return fail(WL_E_ARG, "wl_regions: bad cmp (WL_RG_BELOW or WL_RG_ABOVE)", __FILE__, __LINE__);
+    if (std::isnan(c)) return fail(WL_E_ARG, "wl_regions: the level c must not be NaN", __FILE__, __LINE__);
+    if (periodic_mask < 0 || periodic_mask >= (1 << D)) return fail(WL_E_ARG, "wl_regions: bad periodic_mask (bits 0 .. D - 1)", __FILE__, __LINE__);
+    if (cap < 0) return fail(WL_E_ARG, "wl_regions: negative capacity", __FILE__, __LINE__);
+    if (cap > 0 && (!tab_dev || !ext_dev)) return fail(WL_E_ARG, "wl_regions: null table or extremes with cap > 0", __FILE__, __LINE__);
+    if (cap > ((int64_t)1 << 31)) cap = (int64_t)1 << 31;      // (there are fewer regions than cells)
+    if (((uintptr_t)scratch_dev & 7u) || ((uintptr_t)n_dev & 7u) || ((uintptr_t)tab_dev & 7u) || ((uintptr_t)ext_dev & 7u) || ((uintptr_t)label_dev & 3u))
+        return fail(WL_E_ARG, "wl_regions: a buffer is not aligned to its element", __FILE__, __LINE__);
+    const G gg = mkG(g);
+    int l[3], h[3];
+    WL_TRY(regions_box_args("wl_regions", gg, D, v->kind >= WL_R_METRIC, lo, hi, l, h));
+    if (scratch_bytes < rg_scratch_bytes((long)(h[1] - l[1]) * (h[2] - l[2])))
+        return fail(WL_E_ARG, "wl_regions: fewer bytes of scratch than wl_regions_scratch asks for", __FILE__, __LINE__);
+    WL_DISPATCH(t, D, (op_regions<T, DD>(gg, v, cmp, c, periodic_mask, l, h, label_dev, cap, tab_dev, ext_dev, n_dev, scratch_dev)));
 }
 int wl_tracer_advance(wl_dtype t, const wl_grid *g, const void *u, double *x_dev, int64_t m, double dt, int perdir_mask) {
     WL_TRY(check_grid(g));

@@ -1,0 +1,299 @@
+"""The connected regions of a threshold set, labelled on the device: how many vortices there are, where they are, how big, how
+strong, and which one at step n is the one from step n - 1 -- the member of the read-only family beside the stepper (MeanFlow,
+Probes, Integrals, Forces, SurfaceLoads, Isosurface, Render, Downsample, Histogram, TwoPoint) that treats the cells as a GRAPH.
+A cell is IN when its value -- a stored field, a face pair's mean or a Metrics.jl metric, formed in registers -- is below
+(above) a level; IN cells that share a face are joined; every connected component is a region with a number, a row of integers
+and two extremes.  No scratch field of values, no copy to the host, no flood fill.
+
+    rg = Regions(sim.flow, Value("lambda2"), below=-0.01)          # the vortex cores; the level e.g. from hist.quantile
+    res = table(rg, sim.flow.u)                                    # labels + one row per region (reads the count once)
+    big = select(res, min_cells=50)                                # indices of the regions worth looking at
+    volume(res)[big], centroid(res)[big], bbox(res)[big], peak(res, "min")[0][big]
+    core = mask(res, big[0])                                       # bool, shaped like the box: feed it to Histogram, Render, ...
+    nxt = table(rg2, sim.flow.u); follow(res, nxt)                 # res's regions in nxt's numbering, -1: lost
+    rs = RegionSeries(rg, m=4); record(rs, sim, sim.flow.u); t, rows = series(rs)     # per step, no synchronisation
+
+The kernels and their contract -- kinds, the set, the box, the joins, the numbering, the 13 columns, every refusal -- are in
+include/wlhip.h (wl_regions) and csrc/wl_regions.h; tests/regions_ref.py restates the definition with a breadth-first fill and
+gets the same integers.  Every output is an integer or an extreme: a function of the field, the level and the box alone, bit
+for bit.  Limits: face neighbours only (no edge or corner joins); one rank (a decomposed flow is refused: regions cross ranks);
+no value-weighted sums per region (they need an order contract: DESIGN.md); fewer than 2^31 cells in the box.
+
+The views a result carries alias the object's buffers: the next call overwrites them.  label() does not synchronise; table()
+reads the count once.  volume, centroid, bbox, peak, select, mask and follow are torch operations on whatever device the
+result lives on (a Result may be built from CPU tensors).
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib
+from . import _series
+from . import render
+from . import sim as S
+from ._lib import check
+from .downsample import _DevBuf
+from .twopoint import Value
+
+COLS = 13
+
+
+class Result:
+    """What one labelling gives.  lab: int32, shaped like the box (nx, ny[, nz]) with x fast, -1 or the region's number;
+    tab [R', 13] int64 and ext [R', 2] float64 (include/wlhip.h has the columns); count, cells, nan, visited: 0-d int64
+    tensors (regions, IN cells, NaN cells, cells of the box); lo: the box's low corner (array indices); n: its extents."""
+
+    def __init__(self, lab, tab, ext, count, cells, nan, visited, lo, n):
+        self.lab, self.tab, self.ext = lab, tab, ext
+        self.count, self.cells, self.nan, self.visited = count, cells, nan, visited
+        self.lo, self.n = tuple(int(x) for x in lo), tuple(int(x) for x in n)
+
+    @property
+    def flat(self) -> torch.Tensor:
+        """the labels in the order of the dense index q = (k*ny + j)*nx + i"""
+        return self.lab.permute(*reversed(range(self.lab.dim()))).reshape(-1)
+
+
+class Regions:
+    """The buffers of one (flow, value, level, box, periodic), made and validated once: the int32 label volume of the box, the
+    [capacity, 13] table, the [capacity, 2] extremes, the four counts and the scratch of wl_regions.  Exactly one of below / above
+    (the level c; a cell is IN when v < c / v > c, strictly).  box = (lo, hi): the cells lo_d <= J_d < hi_d, 0-based (default:
+    inside()).  periodic: the axes along which the first and the last cell of every line of the box are joined too.  capacity:
+    the rows of the table (table() grows it; 0: labels and counts only)."""
+
+    def __init__(self, flow, value: Value, below=None, above=None, box=None, periodic=(), capacity: int = 4096):
+        if (below is None) == (above is None):
+            raise ValueError("Regions: give exactly one of below and above")
+        self.flow, self.value, self.D = flow, value, flow.D
+        self.cmp = _lib.WL_RG_BELOW if above is None else _lib.WL_RG_ABOVE
+        self.c = _level(below if above is None else above)
+        sl = flow.layout.slab
+        if sl is not None and sl.size > 1:
+            raise ValueError("Regions: a decomposed flow: regions cross ranks (merging rank-boundary labels is not there yet)")
+        N = tuple(int(x) for x in flow.N)
+        self.box = None
+        lo, hi = (1,) * self.D, tuple(n - 1 for n in N)
+        if box is not None:
+            lo, hi = tuple(int(x) for x in box[0]), tuple(int(x) for x in box[1])
+            if len(lo) != self.D or len(hi) != self.D or any(not (0 <= l < h <= n - 1) for l, h, n in zip(lo, hi, N)):
+                raise ValueError(f"Regions: a box is (lo, hi) with {self.D} entries each, 0 <= lo < hi <= n - 1")
+            self.box = (lo, hi)
+        if value.kind >= render.R_METRIC and min(lo) < 1:
+            raise ValueError("Regions: the box of a metric kind must lie in inside()")
+        self.lo, self.n = lo, tuple(h - l for l, h in zip(lo, hi))
+        self.ncell = int(np.prod(self.n, dtype=np.int64))
+        if self.ncell >= 1 << 31:
+            raise ValueError("Regions: the box holds 2^31 cells or more")
+        axes = sorted(set(int(d) for d in (periodic if hasattr(periodic, "__iter__") else (periodic,))))
+        if any(not 0 <= d < self.D for d in axes):
+            raise ValueError(f"Regions: periodic holds axes 0..{self.D - 1}")
+        self.periodic_mask = sum(1 << d for d in axes)
+        if int(capacity) < 0:
+            raise ValueError("Regions: capacity must be >= 0")
+        self._grid = flow.layout.grid()
+        self._val = _lib.RgValue()
+        self._val.kind, self._val.ipar, self._val.absval = value.kind, value.i, int(getattr(value, "absval", False))
+        self._val.par[:] = list(_lib.d3((0, 0, 0) if value.par is None else value.par))
+        self._val.par2[:] = list(_lib.d3((0, 0, 0) if value.par2 is None else value.par2))
+        nb = C.c_int64()
+        blo, bhi = self._box()
+        check(_lib.lib().wl_regions_scratch(C.byref(self._grid), blo, bhi, C.byref(nb)))
+        self._scratch = _DevBuf(nb.value)
+        self._lab = _DevBuf(4 * self.ncell)
+        self._n = _DevBuf(8 * 4)
+        self._tables(int(capacity))
+
+    def _tables(self, capacity: int) -> None:
+        self.capacity = capacity
+        self._tab = _DevBuf(8 * COLS * capacity) if capacity else None
+        self._ext = _DevBuf(8 * 2 * capacity) if capacity else None
+
+    def _box(self):
+        return (None, None) if self.box is None else (render._i3(self.box[0]), render._i3(self.box[1]))
+
+
+def _level(c) -> float:
+    c = float(c)
+    if c != c:
+        raise ValueError("Regions: the level must not be NaN")
+    return c
+
+
+def label(rg: Regions, field: torch.Tensor, c=None) -> Result:
+    """wl_regions of `field` (u for the component and metric kinds): a Result of device views with R' = capacity rows, of which
+    the rows >= count mean nothing.  c: another level for this call.  No synchronisation."""
+    if S._T(field) != np.dtype(rg.flow.T):
+        raise ValueError("Regions: the field must have the flow's dtype")
+    render._field_grid(rg.flow, field, rg.value.kind != render.R_SCALAR, "Regions")
+    rg._val.f = field.data_ptr()
+    lo, hi = rg._box()
+    cap = rg.capacity
+    check(_lib.lib().wl_regions(S._WLT[S._T(field)], C.byref(rg._grid), C.byref(rg._val), rg.cmp, rg.c if c is None else _level(c),
+                                rg.periodic_mask, lo, hi, C.c_void_p(rg._lab.ptr), cap, C.c_void_p(rg._tab.ptr) if cap else None,
+                                C.c_void_p(rg._ext.ptr) if cap else None, C.c_void_p(rg._n.ptr), C.c_void_p(rg._scratch.ptr),
+                                rg._scratch.nbytes))
+    return _view(rg, cap)
+
+
+def _view(rg: Regions, rows: int) -> Result:
+    dev = rg.flow.device
+    lab = rg._lab.tensor(torch.int32, dev)[:rg.ncell].view(*reversed(rg.n)).permute(*reversed(range(rg.D)))
+    if rg.capacity:
+        tab = rg._tab.tensor(torch.int64, dev)[:COLS * rg.capacity].view(rg.capacity, COLS)[:rows]
+        ext = rg._ext.tensor(torch.float64, dev)[:2 * rg.capacity].view(rg.capacity, 2)[:rows]
+    else:
+        tab, ext = torch.zeros((0, COLS), dtype=torch.int64, device=dev), torch.zeros((0, 2), dtype=torch.float64, device=dev)
+    n = rg._n.tensor(torch.int64, dev)
+    return Result(lab, tab, ext, n[0], n[1], n[2], n[3], rg.lo, rg.n)
+
+
+def table(rg: Regions, field: torch.Tensor, c=None) -> Result:
+    """label(), one read of the count, and the views cut to the R regions there are.  When R > capacity the table and the
+    extremes grow to R and the call is made once more (the labels do not depend on the capacity)."""
+    label(rg, field, c)
+    R = int(rg._n.tensor(torch.int64, rg.flow.device)[0].item())
+    if R > rg.capacity:
+        rg._tables(R)
+        label(rg, field, c)
+    return _view(rg, R)
+
+
+# --------------------------------------------------------------------------- what one reads off the table (any torch device)
+
+def volume(res: Result) -> torch.Tensor:
+    """the cells of every region: [R] int64"""
+    return res.tab[:, 1]
+
+
+def centroid(res: Result) -> torch.Tensor:
+    """[R, D] float64: the mean of the cell centres, sum / cells - 0.5, in the frame x = J - 0.5 of iso and MeshBody.  It means
+    nothing for a region that wraps around a periodic axis (the mean of indices on both sides of the seam)."""
+    D = len(res.n)
+    return res.tab[:, 2:2 + D].to(torch.float64) / res.tab[:, 1:2].to(torch.float64) - 0.5
+
+
+def bbox(res: Result) -> torch.Tensor:
+    """[R, D, 2] int64: the smallest and the largest array index of the region's cells along every axis (both included)"""
+    D = len(res.n)
+    return res.tab[:, 5:5 + 2 * D].reshape(-1, D, 2)
+
+
+def position(res: Result, q: torch.Tensor) -> torch.Tensor:
+    """the array indices [.., D] (the frame of the box arguments) of the dense indices q"""
+    out, q = [], q.to(torch.int64)
+    for d in range(len(res.n)):
+        out.append(res.lo[d] + q % res.n[d])
+        q = torch.div(q, res.n[d], rounding_mode="floor")
+    return torch.stack(out, dim=-1)
+
+
+def peak(res: Result, which: str = "min") -> Tuple[torch.Tensor, torch.Tensor]:
+    """(value [R] float64, array indices [R, D] int64) of every region's minimum ("min") or maximum ("max"); where several
+    cells attain it, the one with the smallest dense index"""
+    if which not in ("min", "max"):
+        raise ValueError('peak: which is "min" or "max"')
+    k = 0 if which == "min" else 1
+    return res.ext[:, k], position(res, res.tab[:, 11 + k])
+
+
+def select(res: Result, min_cells: int = 1, touching_box: Optional[bool] = None) -> torch.Tensor:
+    """The numbers of the regions with at least min_cells cells; touching_box: None: all of them, True: only those with a cell
+    on a face of the box (cut by it, probably), False: only those without.  [.] int64."""
+    keep = res.tab[:, 1] >= int(min_cells)
+    if touching_box is not None:
+        D = len(res.n)
+        bb = bbox(res)
+        lo = torch.tensor(res.lo[:D], dtype=torch.int64, device=res.tab.device)
+        hi = lo + torch.tensor(res.n[:D], dtype=torch.int64, device=res.tab.device) - 1
+        touch = ((bb[:, :, 0] == lo) | (bb[:, :, 1] == hi)).any(dim=1)
+        keep = keep & (touch if touching_box else ~touch)
+    return torch.nonzero(keep).reshape(-1)
+
+
+def mask(res: Result, r) -> torch.Tensor:
+    """bool, shaped like the box: the cells of region r"""
+    return res.lab == int(r)
+
+
+def follow(prev: Result, now: Result, which: str = "min") -> torch.Tensor:
+    """For every region of `prev`, the number in `now` of the cell where its peak (minimum or maximum) was: -1: lost (the cell
+    is not IN any more).  One gather; both results must be of the same box.  [R_prev] int64.  A row of `prev` beyond its
+    count gives -1."""
+    if which not in ("min", "max"):
+        raise ValueError('follow: which is "min" or "max"')
+    if prev.lo != now.lo or prev.n != now.n:
+        raise ValueError("follow: the two results are of different boxes")
+    q = prev.tab[:, 11 if which == "min" else 12]
+    live = torch.arange(q.numel(), device=q.device) < prev.count
+    got = now.flat[torch.where(live, q, torch.zeros_like(q))].to(torch.int64)
+    return torch.where(live, got, torch.full_like(got, -1))
+
+
+# --------------------------------------------------------------------------- over time
+
+SCOLS = COLS + 2
+
+
+class RegionSeries(_series.Series):
+    """Recorder of one Regions object: row k = (regions, IN cells, NaN cells, cells visited, then the m largest regions, largest
+    first and equal sizes by ascending number, 15 numbers each: the 13 columns of the table and the two extremes), as Float64
+    (integers are exact below 2^53).  A step with fewer than m regions leaves NaN in the rows that are missing.  Only the first
+    `capacity` regions of the Regions object are seen: make it large enough (column 0 tells)."""
+
+    def __init__(self, rg: Regions, m: int = 8, capacity: int = 64):
+        if int(m) < 0:
+            raise ValueError("RegionSeries: m must be >= 0")
+        self.m = int(m)
+        super().__init__(("RegionSeries", "the recorder was"), rg.D, rg.flow.layout.slab, (4 + SCOLS * self.m,), capacity, rg.flow.device)
+        self.rg = rg
+
+
+def largest(res: Result, m: int) -> torch.Tensor:
+    """[m, 15] float64: the rows (table, extremes) of the m largest regions among the rows below count, largest first, equal
+    sizes by ascending number; NaN rows where there are fewer.  No synchronisation."""
+    rows = res.tab.shape[0]
+    out = torch.full((m, SCOLS), float("nan"), dtype=torch.float64, device=res.tab.device)
+    mm = min(m, rows)
+    if mm == 0:
+        return out
+    live = torch.arange(rows, device=res.tab.device) < res.count
+    size = torch.where(live, res.tab[:, 1], torch.full_like(res.tab[:, 1], -1))
+    order = torch.sort(size, descending=True, stable=True).indices[:mm]
+    both = torch.cat([res.tab[order].to(torch.float64), res.ext[order]], dim=1)
+    out[:mm] = torch.where((size[order] >= 0).unsqueeze(1), both, out[:mm])
+    return out
+
+
+def record(rs: RegionSeries, sim_or_flow, field: torch.Tensor) -> None:
+    """Append the regions of `field` now: one label() and torch copies into the next row, no synchronisation."""
+    flow = getattr(sim_or_flow, "flow", sim_or_flow)
+    row = _series.next_row(rs, flow.D, flow.layout.slab)
+    res = label(rs.rg, field)
+    row[:4].copy_(rs.rg._n.tensor(torch.int64, flow.device)[:4])
+    if rs.m:
+        row[4:].copy_(largest(res, rs.m).reshape(-1))
+    rs.t.append(S.sim_time(sim_or_flow) if sim_or_flow is not flow else S.time(flow))
+
+
+def series(rs: RegionSeries) -> Tuple[np.ndarray, np.ndarray]:
+    """(t[K], rows[K, 4 + 15*m]) of the K records so far (synchronises).  rows[k, 4:] reshaped to [m, 15] are the largest
+    regions of record k."""
+    t, parts = _series.rank_rows(rs)
+    return t, parts[0]
+
+
+reset = _series.reset
+
+
+def lambda2(rg: Regions, sim, c=None) -> Result:
+    """table() of the lambda2 cores of sim.flow -- the twin of iso.lambda2, without its scratch field: rg was made with
+    Value("lambda2") and below=...; c: another level for this call (hist.quantile picks one)."""
+    if sim.flow is not rg.flow:
+        raise ValueError("Regions: the simulation's flow differs from the one the object was made for")
+    if rg.value.kind != render._KIND["lambda2"] or rg.cmp != _lib.WL_RG_BELOW:
+        raise ValueError('Regions: lambda2 needs Regions(flow, Value("lambda2"), below=c)')
+    return table(rg, sim.flow.u, c)

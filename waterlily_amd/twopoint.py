@@ -41,10 +41,12 @@ COLS, MAX_LINE = 10, 1024
 class Value:
     """One of the two values of a pair.  kind: "scalar" (a scalar field), "ucomp" / "centre" (component i of a vector field, as
     stored / averaged to the cell centre) or a metric of u: "ke", "curl", "omega_mag", "omega_theta", "lambda2" (i, par, par2
-    as waterlily_amd.sim.metric): the kinds of hist.Axis."""
+    as waterlily_amd.sim.metric): the kinds of hist.Axis.  absval: |v| in place of v -- read by Regions, which shares this
+    descriptor; TwoPoint refuses it."""
 
-    def __init__(self, kind="scalar", i: int = 0, par=None, par2=None):
+    def __init__(self, kind="scalar", i: int = 0, par=None, par2=None, absval: bool = False):
         self.kind, self.i, self.par, self.par2 = render._code(render._KIND, kind), int(i), par, par2
+        self.absval = bool(absval)
 
 
 class TwoPoint:
@@ -58,6 +60,8 @@ class TwoPoint:
         self.axis, self.periodic = int(axis), bool(periodic)
         if not 0 <= self.axis < self.D:
             raise ValueError(f"TwoPoint: axis is 0..{self.D - 1}")
+        if a.absval or (b is not None and b.absval):
+            raise ValueError("TwoPoint: a Value with absval=True (wl_twopoint has no such switch)")
         sl = flow.layout.slab
         if self.axis == 2 and sl is not None and sl.size > 1:
             raise ValueError("TwoPoint: axis 2 of a flow decomposed along z: the lines cross ranks")
