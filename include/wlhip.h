@@ -753,7 +753,7 @@ int wl_twopoint(wl_dtype t, const wl_grid *g, const wl_tp_value *a, const wl_tp_
  *   order : none.  Every column is an integer count, an integer sum, an integer extreme or an extreme of an order-preserving
  *           integer image, formed with integer atomics: the same bits on any launch shape.  No floating-point atomics anywhere.
  *           Value-weighted sums per region (the circulation or the enstrophy of a vortex) are deliberately NOT in this table:
- *           a floating-point sum needs an order contract per region.  That is the next step.
+ *           a floating-point sum needs an order contract per region.  wl_region_sums (below) forms them as exact integers.
  *   slabs : a decomposed flow (a z-slab grid, more than one rank) is refused: regions cross ranks, and merging the labels along
  *           the rank boundaries is a later addition.
  * The method: union-find over the dense indices by label equivalence, the parent array being label_dev itself (csrc/wl_regions.h,
@@ -776,6 +776,54 @@ int wl_regions_scratch(const wl_grid *g, const int32_t lo[3], const int32_t hi[3
 int wl_regions(wl_dtype t, const wl_grid *g, const wl_rg_value *v, int cmp, double c, int periodic_mask, const int32_t lo[3],
                const int32_t hi[3], int32_t *label_dev, int64_t cap, int64_t *tab_dev, double *ext_dev, int64_t *n_dev, void *scratch_dev,
                int64_t scratch_bytes);
+
+/* ------------------------------------------------------------------ value-weighted sums per region (regions.sums, waterlily_amd/regions.py)
+ * How strong the regions of a wl_regions call are: per region and column, the sum over its cells of a TERM -- the circulation,
+ * the enstrophy, a weighted moment.  The sum is formed in integers, so it needs no order: the same bits on any launch shape.
+ *   inputs : the box is the box of the wl_regions call that wrote label_dev (nx*ny*nz int32, -1 or a region's number < R) and
+ *           n_dev (its four counts; n_dev[0] = R is read on the device).  A cell takes part when its label is r >= 0.  The
+ *           columns of one call may read different fields (p and u); all of them lie on grid g.
+ *   term  : w = v (power 1) or v * v (power 2), v the value of the cell formed by the device function of wl_regions (kinds as
+ *           there, absval honoured; WL_R_FACE refused); term = w (moment -1) or w * (double)J_d (moment d in 0..D-1, J_d the
+ *           0-based array index of the cell along axis d: the frame of tab_dev's columns 2..4).  Every operation is one IEEE
+ *           double operation; nothing is contracted.
+ *   scale : per column c an int32 E_c in scale_dev[c].  WL_RS_FIND: the call writes E_c = max(ilogb(M_c), WL_RS_EMIN), M_c the
+ *           largest finite |term| over ALL cells with r >= 0 (not only r < cap: the result does not depend on cap), found with
+ *           atomicMax on the order-preserving integer image of |term|; no finite term, or M_c == 0: E_c = WL_RS_EMIN.  over_dev
+ *           is written as zeros.  WL_RS_GIVEN: scale_dev is read, not written -- the caller fixed the exponents so that the limbs
+ *           of several calls or boxes can be added; a value outside WL_RS_EMIN..1023 is taken as the nearer end.  A finite term
+ *           with |term| >= 2^(E_c + 1) is not added; it is counted in over_dev[c], a count over the cells with r >= 0 of the
+ *           whole box.  A non-zero over_dev[c] means column c is invalid.
+ *   fixed point : a finite term maps to the integer n = trunc(term * 2^(126 - E_c)), rounded toward zero: |n| < 2^127; scaling a
+ *           double by a power of two is exact, only the bits below the unit 2^(E_c - 126) are cut.  With |n| = d3*2^96 +
+ *           d2*2^64 + d1*2^32 + d0, 0 <= d_k < 2^32, the cell adds sign(n)*d_k to limb k of its region's column.  A box has
+ *           fewer than 2^31 cells, so |limb| < 2^63.  A term that is not finite (NaN, +-inf) is not added: it adds 1 to the
+ *           fifth entry.
+ *   acc_dev : cap x ncol x 5 int64, acc_dev[(r*ncol + c)*5 + k]: k = 0..3 the limbs, low to high, k = 4 the count of non-finite
+ *           terms.  Rows r < min(R, cap) are initialised by the call, on the device; the other rows are not written, and cells
+ *           with a label >= cap are skipped (they still count for the scale and for over_dev).
+ *   sum_dev : cap x ncol doubles: with N = sum_k limb_k * 2^(32 k) (a signed integer of up to 159 bits), N * 2^(E_c - 126)
+ *           rounded ONCE, to nearest-even; NaN when the count of non-finite terms is not zero; N == 0 gives +0.  The unit is at
+ *           least 2^-1020, so a non-zero result is never subnormal; a magnitude beyond the largest double rounds to +-inf.
+ *           Hence |sum - sum of the terms| <= cells_r * 2^(E_c - 126) + ulp(sum)/2.  Terms more than 2^74 times smaller than
+ *           the column's largest lose low bits; terms more than 2^127 times smaller vanish.
+ *   order : none.  Integer atomics only; during a WL_RS_FIND call over_dev holds the integer images of the maxima.
+ * Refused with WL_E_ARG before the device is touched: NULL g, label_dev, n_dev, cols, scale_dev, acc_dev, sum_dev or over_dev;
+ * ncol outside 1..WL_RS_MAX_COLS; cap < 1; power not 1 or 2; moment outside -1..D-1; a NULL field, an unknown kind or
+ * component, WL_R_FACE, a metric box outside inside(); only one of lo and hi, a bad or empty box, a box of 2^31 cells or more; a
+ * buffer not aligned to its element; an unknown t or scale_mode; a z-slab grid.  Asynchronous on the library's stream: three
+ * launches (WL_RS_GIVEN) or four (WL_RS_FIND), whatever the data; nothing allocated, nothing read back (csrc/wl_region_sums.h).
+ * WaterLily v1.3 has no such function to override. */
+typedef struct {
+    wl_rg_value v;      /* the value, formed by the same device function as everywhere (absval honoured) */
+    int32_t power;      /* 1: w = v;  2: w = v*v  (one IEEE double multiply) */
+    int32_t moment;     /* -1: term = w;  d in 0..D-1: term = w * (double)J_d  (one more IEEE double multiply) */
+} wl_rs_col;
+enum { WL_RS_FIND = 0, WL_RS_GIVEN = 1 };
+enum { WL_RS_MAX_COLS = 8, WL_RS_EMIN = -894 };
+int wl_region_sums(wl_dtype t, const wl_grid *g, const int32_t lo[3], const int32_t hi[3], const int32_t *label_dev,
+                   const int64_t *n_dev, int64_t cap, int ncol, const wl_rs_col *cols, int scale_mode, int32_t *scale_dev,
+                   int64_t *acc_dev, double *sum_dev, int64_t *over_dev);
 
 /* ------------------------------------------------------------------ snapshots (VTK write / restart,ext/WaterLilyWriteVTKExt.jl:57-66,
  * ext/WaterLilyReadVTKExt.jl:28-45).  The reference copies whole fields to the host (`a.flow.u |> Array`) and permutes the vector

@@ -73,6 +73,15 @@ class RgValue(C.Structure):
 WL_RG_BELOW, WL_RG_ABOVE = 0, 1
 
 
+class RsCol(C.Structure):
+    """wl_rs_col (include/wlhip.h): one column of wl_region_sums: the value, its power and the index it is weighted with"""
+    _fields_ = [("v", RgValue), ("power", C.c_int32), ("moment", C.c_int32)]
+
+
+WL_RS_FIND, WL_RS_GIVEN = 0, 1
+WL_RS_MAX_COLS, WL_RS_EMIN = 8, -894
+
+
 WL_BODY_SPHERE, WL_BODY_TORUS, WL_BODY_PLATE, WL_BODY_CYLINDER = 0, 1, 2, 3
 WL_BODY_OP_UNION, WL_BODY_OP_MINUS, WL_BODY_OP_INTERSECT = 0, 1, 2
 WL_BODY_MAXLEAF = 6
@@ -257,6 +266,7 @@ def lib() -> C.CDLL:
         "wl_twopoint_scratch": (i, [gp, i, i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
         "wl_regions": (i, [i, gp, vp, i, d, i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, i64, vp, vp, vp, vp, i64]),      # (v: byref(RgValue))
         "wl_regions_scratch": (i, [gp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+        "wl_region_sums": (i, [i, gp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, vp, i64, i, vp, i, vp, vp, vp, vp]),      # (cols: an array of RsCol)
         "wl_snapshot_pack": (i, [i, gp, vp, i, i, i, i, vp]),
         "wl_snapshot_unpack": (i, [i, gp, vp, i, i, i, i, vp]),
         "wl_set_option": (i, [i, i]),

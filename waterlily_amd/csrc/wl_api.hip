@@ -25,6 +25,7 @@
 #include "wl_hist.h"
 #include "wl_twopoint.h"
 #include "wl_regions.h"
+#include "wl_region_sums.h"
 
 namespace wl {
 
@@ -1865,6 +1866,34 @@ int wl_regions(wl_dtype t, const wl_grid *g, const wl_rg_value *v, int cmp, doub
     if (scratch_bytes < rg_scratch_bytes((long)(h[1] - l[1]) * (h[2] - l[2])))
         return fail(WL_E_ARG, "wl_regions: fewer bytes of scratch than wl_regions_scratch asks for", __FILE__, __LINE__);
     WL_DISPATCH(t, D, (op_regions<T, DD>(gg, v, cmp, c, periodic_mask, l, h, label_dev, cap, tab_dev, ext_dev, n_dev, scratch_dev)));
+}
+int wl_region_sums(wl_dtype t, const wl_grid *g, const int32_t lo[3], const int32_t hi[3], const int32_t *label_dev, const int64_t *n_dev,
+                   int64_t cap, int ncol, const wl_rs_col *cols, int scale_mode, int32_t *scale_dev, int64_t *acc_dev, double *sum_dev,
+                   int64_t *over_dev) {
+    if (!g || !label_dev || !n_dev || !cols || !scale_dev || !acc_dev || !sum_dev || !over_dev)
+        return fail(WL_E_ARG, "wl_region_sums: null grid, labels, counts, columns, scale, limbs, sums or overflow counts", __FILE__, __LINE__);
+    WL_TRY(check_grid(g));
+    WL_TRY(check_dtype("wl_region_sums", t));
+    if (scale_mode != WL_RS_FIND && scale_mode != WL_RS_GIVEN) return fail(WL_E_ARG, "wl_region_sums: bad scale_mode (WL_RS_FIND or WL_RS_GIVEN)", __FILE__, __LINE__);
+    if (ncol < 1 || ncol > WL_RS_MAX_COLS) return fail(WL_E_ARG, "wl_region_sums: bad ncol (1 .. WL_RS_MAX_COLS = 8)", __FILE__, __LINE__);
+    if (cap < 1) return fail(WL_E_ARG, "wl_region_sums: the capacity must be >= 1", __FILE__, __LINE__);
+    if (cap > ((int64_t)1 << 31)) cap = (int64_t)1 << 31;      // (there are fewer regions than cells)
+    const int D = g->D;
+    bool metric = false;
+    for (int c = 0; c < ncol; ++c) {
+        if (!cols[c].v.f) return fail(WL_E_ARG, "wl_region_sums: null field of a column's value", __FILE__, __LINE__);
+        WL_TRY(check_kind("wl_region_sums", cols[c].v.kind, cols[c].v.ipar, D, false));
+        if (cols[c].power != 1 && cols[c].power != 2) return fail(WL_E_ARG, "wl_region_sums: bad power (1 or 2)", __FILE__, __LINE__);
+        if (cols[c].moment < -1 || cols[c].moment >= D) return fail(WL_E_ARG, "wl_region_sums: bad moment (-1 or an axis 0 .. D - 1)", __FILE__, __LINE__);
+        metric = metric || cols[c].v.kind >= WL_R_METRIC;
+    }
+    if (((uintptr_t)label_dev & 3u) || ((uintptr_t)scale_dev & 3u) || ((uintptr_t)n_dev & 7u) || ((uintptr_t)acc_dev & 7u) || ((uintptr_t)sum_dev & 7u) ||
+        ((uintptr_t)over_dev & 7u))
+        return fail(WL_E_ARG, "wl_region_sums: a buffer is not aligned to its element", __FILE__, __LINE__);
+    const G gg = mkG(g);
+    int l[3], h[3];
+    WL_TRY(regions_box_args("wl_region_sums", gg, D, metric, lo, hi, l, h));
+    WL_DISPATCH(t, D, (op_region_sums<T, DD>(gg, l, h, label_dev, n_dev, cap, ncol, cols, scale_mode, scale_dev, acc_dev, sum_dev, over_dev)));
 }
 int wl_tracer_advance(wl_dtype t, const wl_grid *g, const void *u, double *x_dev, int64_t m, double dt, int perdir_mask) {
     WL_TRY(check_grid(g));
