@@ -558,6 +558,65 @@ int wl_render_shade(const double *img_dev, int64_t ld, int nx, int ny, double vm
                     const double *mask_dev, int64_t ldm, double mask_lt, const uint8_t mask_rgba[4], const uint8_t nan_rgba[4], int zoom,
                     int flip_y, uint8_t *rgba_dev);
 
+/* ------------------------------------------------------------------ depth-buffered pictures of triangles (Scene, waterlily_amd/scene.py)
+ * A small rasteriser for what wl_isosurface and a posed MeshBody yield: triangles tri_dev[nt][3][3] (doubles, the frame
+ * x = J - 0.5), optional vertex values val_dev[nt][3], a camera M (row-major 4x4 doubles made on the host, clip = M (x,y,z,1)), an
+ * image of W x H pixels (both 1..WL_SCENE_MAX_SIZE) and a depth buffer key_dev[H*W] of uint64.  Row 0 is the top of the picture.
+ * Every double operation below is its own IEEE operation in the order written; coverage and depth order are integers, so the
+ * keys are a function of the triangles and the camera alone, bit for bit (tests/scene_ref.py restates all of it).
+ *   clear   : wl_scene_clear sets every key to all ones: "nothing".
+ *   vertex  : per vertex (x, y, z): c_r = ((M[r][0]*x + M[r][1]*y) + M[r][2]*z) + M[r][3], r = 0..3.  The triangle is dropped whole
+ *             when a coordinate or a c is not finite, when a c_3 <= 0, or when a z_ndc = c_2/c_3 is not in [0, 1]: THERE IS NO
+ *             CLIPPING -- keep the near and far planes clear of the surface, and the eye outside it.  Then
+ *             s_x = ((c_0/c_3)*0.5 + 0.5)*W, s_y = (0.5 - (c_1/c_3)*0.5)*H; dropped unless |s_x| < 2^19 and |s_y| < 2^19;
+ *             X = (int64)floor(s_x*256 + 0.5), Y = (int64)floor(s_y*256 + 0.5): 8 sub-pixel bits.
+ *   cover   : int64 only.  Pixel (i, j) (column, row) has the centre P = (256 i + 128, 256 j + 128).  E_ab(P) = (X_b - X_a)(P_y - Y_a) -
+ *             (Y_b - Y_a)(P_x - X_a).  A2 = E_01(V_2); A2 == 0 drops the triangle; A2 < 0 exchanges vertices 1 and 2 (with their
+ *             z_ndc, c_3 and values) and negates A2, so both windings are drawn.  E_0 = E_12(P), E_1 = E_20(P), E_2 = E_01(P) (E_k
+ *             is opposite vertex k).  The pixel is covered when every E_k > 0, or == 0 on a top or left edge: edge a -> b is left
+ *             when Y_b < Y_a and top when Y_b == Y_a and X_b > X_a (after the exchange; y grows downwards).  A centre on an edge
+ *             that two triangles share belongs to exactly one of them.  Pixels visited: the centres inside the bounding box of
+ *             the three (X, Y), i from (min X + 127) >> 8 to (max X - 128) >> 8, j likewise, both clamped to the viewport.
+ *   key     : b_k = (double)E_k / (double)A2; d = (b_0*z_0 + b_1*z_1) + b_2*z_2 (z_k the z_ndc); zq = floor(d * 2^32) clamped to
+ *             [0, 2^32 - 1]; key = (uint64)zq << 32 | (base + t), t the triangle's number in this draw.  The pixel takes the
+ *             unsigned minimum (a 64-bit integer atomic): the nearest surface wins, equal depth goes to the lower id.  base + nt
+ *             <= 2^32 - 1, so no key is all ones.  Draws with disjoint id ranges share one depth buffer.
+ *   paths   : a triangle whose clamped bounding box holds at most large_px pixels is rasterised by one lane; the others are
+ *             appended (one integer atomic per wavefront) to a list in scratch_dev and a second launch gives each a whole
+ *             wavefront, whose lanes tile the box 8 x 8 pixels at a time.  Neither the choice nor the order of the list shows in
+ *             the keys.  large_px == 0: every triangle takes the wavefront path; large_px >= W*H: every triangle its lane.
+ *             wl_scene_scratch: the bytes of scratch_dev for nt triangles (16 + 4 nt), host arithmetic.
+ *   shade   : wl_scene_shade writes rgba_dev[H*W*4] at the pixels whose key holds an id in [base, base + nt) and touches no other
+ *             pixel.  tri_dev, val_dev, M, W, H, base must be the draw's.  The E_k and b_k are recomputed from the same integers.
+ *             Value, perspective-correct: q_k = b_k / c_3,k; v = ((q_0*v_0 + q_1*v_1) + q_2*v_2) / ((q_0 + q_1) + q_2).  A NaN v
+ *             gives nan_rgba (NULL: 0,0,0,0) as it is, unlit.  Otherwise the colour is lut_dev[idx], idx by wl_render_shade's rule
+ *             from (v, vmin, vmax, levels) (one device function serves both); without val_dev it is solid_rgba.  Lighting,
+ *             flat and two-sided, from the triangle as stored: a = V_1 - V_0, b = V_2 - V_0, n = (a_y*b_z - a_z*b_y, a_z*b_x - a_x*b_z,
+ *             a_x*b_y - a_y*b_x), len = sqrt((n_x*n_x + n_y*n_y) + n_z*n_z), s = ambient + (1 - ambient) * |((n_x*l_x + n_y*l_y) +
+ *             n_z*l_z) / len| (len == 0: s = ambient); a channel c becomes floor(c*s + 0.5) clamped to 0..255; alpha is 255.  The
+ *             sqrt is the one operation not held to a correctly rounded result.  light: a unit vector, host array.
+ *   resolve : wl_scene_resolve: a pixel whose key is "nothing" counts as background_rgba, any other as rgba_dev's; every
+ *             ssaa x ssaa block (ssaa 1, 2 or 4; W and H multiples of it) becomes one pixel of out_dev[(H/ssaa)*(W/ssaa)*4], per
+ *             channel (sum + n/2) / n in integers, n = ssaa^2.  Anti-aliasing is drawing at ssaa times the size.
+ * Refused with WL_E_ARG before the device is touched: a NULL key_dev, scratch_dev, M, light, rgba_dev, out_dev or
+ * background_rgba; NULL tri_dev with nt > 0; W or H outside 1..4096; nt < 0; base + nt > 2^32 - 1; a camera entry that is not
+ * finite; large_px < 0; scratch_bytes below wl_scene_scratch's; val_dev without lut_dev, with vmin >= vmax or either not finite,
+ * or levels outside 0..256; neither val_dev nor solid_rgba; ambient outside [0, 1]; a light that is not finite; ssaa other than
+ * 1, 2, 4 or not dividing W and H; an output that is not 4-byte aligned.  Asynchronous on the library's stream; nothing is
+ * allocated, no LDS, no float atomics.  The triangles of a draw must stay unchanged until its wl_scene_shade has run.  A
+ * decomposed flow has no distributed picture: draw what the ranks' triangles gathered on one rank give.  WaterLily v1.3 draws
+ * on the host (Makie): these entry points are there for a later binding. */
+enum { WL_SCENE_MAX_SIZE = 4096 };
+int wl_scene_clear(uint64_t *key_dev, int W, int H);
+int wl_scene_scratch(int64_t nt, int64_t *bytes);
+int wl_scene_draw(uint64_t *key_dev, int W, int H, const double M[16], const double *tri_dev, int64_t nt, uint32_t base, int64_t large_px,
+                  void *scratch_dev, int64_t scratch_bytes);
+int wl_scene_shade(const uint64_t *key_dev, int W, int H, uint32_t base, int64_t nt, const double *tri_dev, const double *val_dev,
+                   const double M[16], double vmin, double vmax, int levels, const uint8_t *lut_dev, const uint8_t solid_rgba[4],
+                   const double light[3], double ambient, const uint8_t nan_rgba[4], uint8_t *rgba_dev);
+int wl_scene_resolve(const uint8_t *rgba_dev, int W, int H, const uint64_t *key_dev, int ssaa, const uint8_t background_rgba[4],
+                     uint8_t *out_dev);
+
 /* ------------------------------------------------------------------ box-filtered, cropped volumes (Downsampler, waterlily_amd/downsample.py)
  * The 3-D counterpart of wl_render_project: the fine cells lo_d <= J_d < hi_d (0-based, z global) are cut into blocks of
  * factor^D cells and every block becomes one coarse cell, its value formed on the fly from f.  No volume is filled first: a

@@ -10,5 +10,7 @@ from .probes import Probes, Tracers, interp  # noqa: F401
 from . import regions  # noqa: F401
 from .regions import Regions, RegionSeries  # noqa: F401
 from .render import Renderer  # noqa: F401
+from . import scene  # noqa: F401
+from .scene import Camera, Scene  # noqa: F401
 from . import twopoint  # noqa: F401
 from .twopoint import TwoPoint, Value  # noqa: F401

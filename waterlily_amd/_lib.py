@@ -257,6 +257,11 @@ def lib() -> C.CDLL:
         "wl_isosurface": (i, [i, gp, vp, vp, d, C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, vp, i64, vp]),
         "wl_render_project": (i, [i, gp, vp, i, i, dp, dp, i, i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, i64]),
         "wl_render_shade": (i, [vp, i64, i, i, d, d, i, vp, vp, i64, d, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), i, i, vp]),
+        "wl_scene_clear": (i, [vp, i, i]),
+        "wl_scene_scratch": (i, [i64, C.POINTER(i64)]),
+        "wl_scene_draw": (i, [vp, i, i, dp, vp, i64, C.c_uint32, i64, vp, i64]),
+        "wl_scene_shade": (i, [vp, i, i, C.c_uint32, i64, vp, vp, dp, d, d, i, vp, C.POINTER(C.c_uint8), dp, d, C.POINTER(C.c_uint8), vp]),
+        "wl_scene_resolve": (i, [vp, i, i, vp, i, C.POINTER(C.c_uint8), vp]),
         "wl_downsample": (i, [i, gp, vp, i, i, dp, dp, i, i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), i, vp, i, i]),
         "wl_downsample_extent": (i, [gp, i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
         "wl_histogram": (i, [i, gp, vp, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), i, vp]),      # (a, b: byref(HistAxis))

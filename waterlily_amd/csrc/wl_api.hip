@@ -26,6 +26,7 @@
 #include "wl_twopoint.h"
 #include "wl_regions.h"
 #include "wl_region_sums.h"
+#include "wl_scene.h"
 
 namespace wl {
 
@@ -1691,6 +1692,82 @@ int wl_render_shade(const double *img_dev, int64_t ld, int nx, int ny, double vm
     A.ld = ld; A.ldm = ldm; A.nx = nx; A.ny = ny; A.levels = levels; A.zoom = zoom; A.flip_y = flip_y ? 1 : 0; A.masked = mask_dev ? 1 : 0;
     A.vmin = vmin; A.vmax = vmax; A.mask_lt = mask_lt; A.mask_rgba = mask_dev ? word(mask_rgba) : 0u; A.nan_rgba = word(nan_rgba);
     return op_render_shade(A, img_dev, mask_dev, lut_dev, rgba_dev);
+}
+// the checks every wl_scene_* entry shares: the image extents
+static int scene_size(const char *who, int W, int H) {
+    if (W < 1 || W > WL_SCENE_MAX_SIZE || H < 1 || H > WL_SCENE_MAX_SIZE) WL_BAD(who, "W and H must lie in 1..4096");
+    return 0;
+}
+// ... and the triangles of one draw with their ids base .. base + nt - 1
+static int scene_tris(const char *who, int64_t nt, uint32_t base, const double *tri_dev, const double M[16], SceneCam *C) {
+    if (nt < 0) WL_BAD(who, "negative nt");
+    if ((uint64_t)base + (uint64_t)nt > 0xFFFFFFFFull) WL_BAD(who, "base + nt must not exceed 2^32 - 1 (the triangle ids of one picture)");
+    if (nt > 0 && !tri_dev) WL_BAD(who, "null triangles with nt > 0");
+    if (!M) WL_BAD(who, "null camera matrix");
+    for (int k = 0; k < 16; ++k) {
+        if (!std::isfinite(M[k])) WL_BAD(who, "the camera matrix must be finite");
+        C->m[k] = M[k];
+    }
+    return 0;
+}
+int wl_scene_clear(uint64_t *key_dev, int W, int H) {
+    if (!key_dev) return fail(WL_E_ARG, "wl_scene_clear: null keys", __FILE__, __LINE__);
+    WL_TRY(scene_size("wl_scene_clear", W, H));
+    return op_scene_clear((unsigned long long *)key_dev, W, H);
+}
+int wl_scene_scratch(int64_t nt, int64_t *bytes) {
+    if (!bytes || nt < 0 || nt > 0xFFFFFFFFll) return fail(WL_E_ARG, "wl_scene_scratch: null bytes or nt outside 0..2^32 - 1", __FILE__, __LINE__);
+    *bytes = scene_scratch_bytes(nt);
+    return 0;
+}
+int wl_scene_draw(uint64_t *key_dev, int W, int H, const double M[16], const double *tri_dev, int64_t nt, uint32_t base, int64_t large_px,
+                  void *scratch_dev, int64_t scratch_bytes) {
+    if (!key_dev || !scratch_dev) return fail(WL_E_ARG, "wl_scene_draw: null keys or scratch", __FILE__, __LINE__);
+    WL_TRY(scene_size("wl_scene_draw", W, H));
+    SceneCam C;
+    WL_TRY(scene_tris("wl_scene_draw", nt, base, tri_dev, M, &C));
+    if (large_px < 0) return fail(WL_E_ARG, "wl_scene_draw: negative large_px", __FILE__, __LINE__);
+    if (scratch_bytes < scene_scratch_bytes(nt)) return fail(WL_E_ARG, "wl_scene_draw: scratch_bytes below wl_scene_scratch's", __FILE__, __LINE__);
+    if (((uintptr_t)scratch_dev & 3u) != 0) return fail(WL_E_ARG, "wl_scene_draw: the scratch must be 4-byte aligned", __FILE__, __LINE__);
+    return op_scene_draw((unsigned long long *)key_dev, W, H, C, tri_dev, nt, base, large_px, (unsigned *)scratch_dev);
+}
+int wl_scene_shade(const uint64_t *key_dev, int W, int H, uint32_t base, int64_t nt, const double *tri_dev, const double *val_dev,
+                   const double M[16], double vmin, double vmax, int levels, const uint8_t *lut_dev, const uint8_t solid_rgba[4],
+                   const double light[3], double ambient, const uint8_t nan_rgba[4], uint8_t *rgba_dev) {
+    if (!key_dev || !rgba_dev || !light) return fail(WL_E_ARG, "wl_scene_shade: null keys, output or light", __FILE__, __LINE__);
+    if (((uintptr_t)rgba_dev & 3u) != 0) return fail(WL_E_ARG, "wl_scene_shade: the output must be 4-byte aligned", __FILE__, __LINE__);
+    WL_TRY(scene_size("wl_scene_shade", W, H));
+    SceneCam C;
+    WL_TRY(scene_tris("wl_scene_shade", nt, base, tri_dev, M, &C));
+    if (val_dev) {
+        if (!lut_dev) return fail(WL_E_ARG, "wl_scene_shade: vertex values need a colour table", __FILE__, __LINE__);
+        if (!(std::isfinite(vmin) && std::isfinite(vmax) && vmin < vmax)) return fail(WL_E_ARG, "wl_scene_shade: need finite vmin < vmax", __FILE__, __LINE__);
+        if (levels < 0 || levels > 256) return fail(WL_E_ARG, "wl_scene_shade: levels must lie in 0..256", __FILE__, __LINE__);
+    } else if (!solid_rgba) {
+        return fail(WL_E_ARG, "wl_scene_shade: no vertex values and no solid colour", __FILE__, __LINE__);
+    }
+    if (!(ambient >= 0.0 && ambient <= 1.0)) return fail(WL_E_ARG, "wl_scene_shade: ambient must lie in 0..1", __FILE__, __LINE__);
+    if (!(std::isfinite(light[0]) && std::isfinite(light[1]) && std::isfinite(light[2])))
+        return fail(WL_E_ARG, "wl_scene_shade: the light direction must be finite", __FILE__, __LINE__);
+    auto word = [](const uint8_t *c) { return c ? (uint32_t)c[0] | ((uint32_t)c[1] << 8) | ((uint32_t)c[2] << 16) | ((uint32_t)c[3] << 24) : 0u; };
+    SceneShade A;
+    A.W = W; A.H = H; A.levels = levels; A.has_val = val_dev ? 1 : 0; A.base = base; A.nt = (long)nt;
+    A.vmin = vmin; A.vmax = vmax; A.ambient = ambient;
+    for (int d = 0; d < 3; ++d) A.light[d] = light[d];
+    A.solid = word(solid_rgba); A.nan_rgba = word(nan_rgba);
+    return op_scene_shade(C, A, (const unsigned long long *)key_dev, tri_dev, val_dev, lut_dev, rgba_dev);
+}
+int wl_scene_resolve(const uint8_t *rgba_dev, int W, int H, const uint64_t *key_dev, int ssaa, const uint8_t background_rgba[4],
+                     uint8_t *out_dev) {
+    if (!rgba_dev || !key_dev || !background_rgba || !out_dev)
+        return fail(WL_E_ARG, "wl_scene_resolve: null frame, keys, background or output", __FILE__, __LINE__);
+    if ((((uintptr_t)rgba_dev | (uintptr_t)out_dev) & 3u) != 0) return fail(WL_E_ARG, "wl_scene_resolve: frame and output must be 4-byte aligned", __FILE__, __LINE__);
+    WL_TRY(scene_size("wl_scene_resolve", W, H));
+    if (ssaa != 1 && ssaa != 2 && ssaa != 4) return fail(WL_E_ARG, "wl_scene_resolve: bad ssaa (1, 2 or 4)", __FILE__, __LINE__);
+    if (W % ssaa != 0 || H % ssaa != 0) return fail(WL_E_ARG, "wl_scene_resolve: W and H must be multiples of ssaa", __FILE__, __LINE__);
+    const uint32_t bg = (uint32_t)background_rgba[0] | ((uint32_t)background_rgba[1] << 8) | ((uint32_t)background_rgba[2] << 16) |
+                        ((uint32_t)background_rgba[3] << 24);
+    return op_scene_resolve(rgba_dev, (const unsigned long long *)key_dev, W, H, ssaa, bg, out_dev);
 }
 // the checks wl_downsample and wl_downsample_extent share: factor and box -> l, h (a box without cells is refused here)
 static int downsample_box(const char *who, const wl_grid *g, const G &gg, int factor, const int32_t lo[3], const int32_t hi[3], int l[3], int h[3]) {

@@ -252,6 +252,22 @@ struct ShadeArgs {
     double vmin, vmax, mask_lt;
     uint32_t mask_rgba, nan_rgba;                              // byte 0 = R (the little-endian word the store writes)
 };
+// the entry of the 256-entry colour table a value v (not NaN) takes: the one statement of wl_render_shade's rule (wl_scene_shade
+// calls it too)
+__device__ __forceinline__ int shade_index(double v, double vmin, double vmax, int levels) {
+    const double t = (v - vmin) / (vmax - vmin);
+    double x;
+    if (levels == 0) {
+        x = floor(t * 256.0);
+        x = x < 0.0 ? 0.0 : (x > 255.0 ? 255.0 : x);
+    } else {
+        const double n = (double)levels;
+        double bnd = floor(t * n);
+        bnd = bnd < 0.0 ? 0.0 : (bnd > n - 1.0 ? n - 1.0 : bnd);
+        x = floor((bnd + 0.5) * 256.0 / n);
+    }
+    return (int)x;
+}
 __global__ __launch_bounds__(256) void k_render_shade(const ShadeArgs A, const double *__restrict__ img, const double *__restrict__ mask,
                                                      const uint8_t *__restrict__ lut, uint32_t *__restrict__ rgba) {
     const long W = (long)A.nx * A.zoom, H = (long)A.ny * A.zoom;
@@ -263,18 +279,7 @@ __global__ __launch_bounds__(256) void k_render_shade(const ShadeArgs A, const d
     if (A.masked && mask[py * A.ldm + px] < A.mask_lt) out = A.mask_rgba;
     else if (v != v) out = A.nan_rgba;
     else {
-        const double t = (v - A.vmin) / (A.vmax - A.vmin);
-        double x;
-        if (A.levels == 0) {
-            x = floor(t * 256.0);
-            x = x < 0.0 ? 0.0 : (x > 255.0 ? 255.0 : x);
-        } else {
-            const double n = (double)A.levels;
-            double bnd = floor(t * n);
-            bnd = bnd < 0.0 ? 0.0 : (bnd > n - 1.0 ? n - 1.0 : bnd);
-            x = floor((bnd + 0.5) * 256.0 / n);
-        }
-        const uint8_t *e = lut + 4 * (int)x;
+        const uint8_t *e = lut + 4 * shade_index(v, A.vmin, A.vmax, A.levels);
         out = (uint32_t)e[0] | ((uint32_t)e[1] << 8) | ((uint32_t)e[2] << 16) | ((uint32_t)e[3] << 24);
     }
     rgba[oy * W + ox] = out;
