@@ -416,6 +416,48 @@ int wl_flow_integrals(wl_dtype t, const wl_grid *g, const void *u, const double 
 int wl_meanflow_update(wl_dtype t_flow, wl_dtype t_acc, const wl_grid *g, const void *u, const void *p, const wl_grid *ga, void *U,
                        void *P, void *UU, void *pp, double eps, int first);
 
+/* ------------------------------------------------------------------ turbulent kinetic energy budget (Budget, waterlily_amd/budget.py)
+ * wl_budget_update: one update of the CENTRAL moments the budget of k = 1/2 <u_i'u_i'> is made of, over every cell I of
+ * inside() (on a z-slab: this rank's owned interior planes; the first halo plane on each side of u and Uf is read, and must
+ * exist).  Uf (D components), Pm: the running means BEFORE this update, the fields U, P of a MeanFlow on grid ga (it averages
+ * ghost cells and halo planes too, so they are current without an exchange).  In double arithmetic, every operand converted
+ * first, one rounding to t_acc per store, with eps = dt / (t - t0) in (0, 1] as for wl_meanflow_update and keep = 1 - eps:
+ *   d[J,i] = u[J,i] - Uf[J,i];   a_i = 0.5 (d[I,i] + d[I+e_i,i])  (the centre fluctuation, as in ke);   q = p[I] - Pm[I]
+ *   h_ij = d(i,j,I,d) of src/Metrics.jl:28-30:  h_ii = d[I+e_i,i] - d[I,i],
+ *          h_ij = (d[I+e_j,i] + d[I+e_j+e_i,i] - d[I-e_j,i] - d[I-e_j+e_i,i]) / 4, added left to right
+ *   s = sum_i a_i a_i;   gg = sum_i sum_j h_ij h_ij (i outer, j inner);   every sum ascending, each term added to the sum so far
+ *   T3_j <- (keep T3_j + ((keep eps (1 - 2 eps)) s) a_j) - (eps keep) (2 sum_i a_i R_ij + a_j sum_i R_ii)   with the OLD R,
+ *   R_q  <- keep (R_q + (eps a_ia) a_ib);   PU_j <- keep (PU_j + (eps q) a_j);   GG <- keep (GG + eps gg)
+ * (the weighted single-sample merge of second and third central moments).  R: the cell-centred covariance <u_i'u_j'>,
+ * D(D+1)/2 components in ParaView's order (3-D xx yy zz xy yz xz, 2-D xx yy xy); PU: <p'u_j'>, D components; GG:
+ * <h_ij h_ij>; T3: <u_i'u_i'u_j'>, D components -- 13 fields in 3-D, 8 in 2-D, on grid ga (same extents and slab as g, the
+ * strides may differ), component stride ga->sc.  first != 0 (eps == 1): every moment becomes 0 and no accumulator, u, p or
+ * mean is read.  Cells outside inside() are never written.  t_flow = WL_F64 with t_acc = WL_F32 is refused.
+ * The means are NOT advanced: the thread of a neighbouring cell reads Uf at the faces of the cell this thread would write, so
+ * the caller follows this launch with wl_meanflow_update (U = Uf, P = Pm), which advances them.  Asynchronous: one launch.
+ *
+ * wl_budget_terms: the budget terms from the moments, one launch over inside(); arithmetic in double, each value rounded once
+ * to t_acc; out has eight components on grid ga (component stride ga->sc).  The cells of inside() shrunk by one on every
+ * side (global indices 2 .. n-3) get, with k[J] = 0.5 ((R_0[J] + R_1[J]) + R_2[J]), D_j f = (f[I+e_j] - f[I-e_j]) / 2,
+ * G_ij = d(i,j,I,Uf) as above, C_j = 0.5 (Uf[I,j] + Uf[I+e_j,j]):
+ *   0  k[I]
+ *   1  production           -(sum_i sum_j R_ij G_ij)            i outer, j inner
+ *   2  dissipation           nu GG[I]                            (positive)
+ *   3  turbulent transport  -0.5 (sum_j D_j T3_j)
+ *   4  pressure transport   -(sum_j D_j PU_j)
+ *   5  viscous diffusion     nu (sum_j ((k[I+e_j] - 2 k[I]) + k[I-e_j]))
+ *   6  convection           -(sum_j C_j D_j k)
+ *   7  residual              ((((t1 - t2) + t3) + t4) + t5) + t6  of the unrounded terms: dk/dt plus what the discretisation
+ *      and the body do not close
+ * every sum ascending, each term added to the sum so far.  The remaining cells of inside() (its rim) get 0; cells outside
+ * inside() are not written.  On a z-slab the planes next to a rank boundary read one halo plane of R, PU and T3: the caller
+ * exchanges them first (wl_halo_exchange).  Asynchronous.  WaterLily v1.3 has no such function to override: the entry points
+ * are there for a later binding. */
+int wl_budget_update(wl_dtype t_flow, wl_dtype t_acc, const wl_grid *g, const void *u, const void *p, const wl_grid *ga, const void *Uf,
+                     const void *Pm, void *R, void *PU, void *GG, void *T3, double eps, int first);
+int wl_budget_terms(wl_dtype t_acc, const wl_grid *ga, const void *Uf, const void *R, const void *PU, const void *GG, const void *T3,
+                    double nu, void *out);
+
 /* ------------------------------------------------------------------ point probes and tracers (waterlily_amd/probes.py)
  * interp(x, arr)  src/util.jl:238-257.  x_dev: m*D doubles, point-major, 1-based index coordinates (global z).
  * ncomp == 0: scalar field; ncomp == D: staggered vector field.  Row q of the result at out_dev + q*ldo (ldo >= max(1,ncomp)).

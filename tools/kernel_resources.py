@@ -58,6 +58,14 @@ def short(d):
         m = re.match(r"(?:float|double), (\d), (true|false)(?:, (\d))?", args)
         if m:
             extra = [f"D={m.group(1)}", f"metric={m.group(2)}"] + ([f"B={('none', 'plain', 'metric')[int(m.group(3))]}"] if m.group(3) else [])
+    elif kern == "k_budget_update":
+        m = re.match(r"(?:float|double), (float|double), (\d)", args)
+        if m:
+            extra = [f"A={'f32' if m.group(1) == 'float' else 'f64'}", f"D={m.group(2)}"]
+    elif "op_budget_terms<" in args:
+        m = re.search(r"op_budget_terms<(float|double), (\d)>", args)
+        if m:
+            extra = [f"A={'f32' if m.group(1) == 'float' else 'f64'}", f"D={m.group(2)}"]
     return " ".join(x for x in [kern, T, op.group(1) if op else "", ("#" + lam[0]) if lam else ""] + extra if x)
 
 

@@ -1,5 +1,7 @@
 """waterlily_amd -- MI355X-native backend for WaterLily's `sim_step!` hot path."""
 from .body import AutoBody, NoBody, measure, norm2  # noqa: F401
+from . import budget  # noqa: F401
+from .budget import Budget  # noqa: F401
 from .downsample import Downsampler, DownsampleWriter  # noqa: F401
 from . import forces  # noqa: F401
 from .forces import Forces  # noqa: F401

@@ -249,6 +249,8 @@ def lib() -> C.CDLL:
         "wl_band_loads": (i, [i, gp, vp, vp, d, vp, vp, i64, dp, vp]),
         "wl_flow_integrals": (i, [i, gp, vp, dp, vp]),
         "wl_meanflow_update": (i, [i, i, gp, vp, vp, gp, vp, vp, vp, vp, d, i]),
+        "wl_budget_update": (i, [i, i, gp, vp, vp, gp, vp, vp, vp, vp, vp, vp, d, i]),
+        "wl_budget_terms": (i, [i, gp, vp, vp, vp, vp, vp, d, vp]),
         "wl_interp": (i, [i, gp, vp, i, vp, i64, vp, i64]),
         "wl_tracer_advance": (i, [i, gp, vp, vp, i64, d, i]),
         "wl_surface_sample": (i, [i, gp, vp, vp, vp, C.POINTER(MeshPose), d, d, vp, vp, vp, d, i]),

@@ -15,6 +15,7 @@
 #include "wl_measure.h"
 #include "wl_mesh.h"
 #include "wl_stats.h"
+#include "wl_budget.h"
 #include "wl_probe.h"
 #include "wl_integrals.h"
 #include "wl_forces.h"
@@ -1593,6 +1594,49 @@ int wl_meanflow_update(wl_dtype t_flow, wl_dtype t_acc, const wl_grid *g, const 
     if (g->D == 3) return WL_MEANFLOW(float, float, 3);
     return WL_MEANFLOW(float, float, 2);
 #undef WL_MEANFLOW
+}
+// ---- Budget (wl_budget.h): every argument check comes before the first device call
+static int check_acc_grid(const char *who, const wl_grid *g, const wl_grid *ga) {
+    bool same = ga->D == g->D && ga->nzg == g->nzg;
+    for (int d = 0; d < 3; ++d) same = same && ga->n[d] == g->n[d];
+    if (same && g->D == 3 && g->nzg > 0)
+        same = ga->kz0 == g->kz0 && ga->own_lo == g->own_lo && ga->own_hi == g->own_hi && ga->zring == g->zring;
+    if (!same) WL_BAD(who, "the accumulators' grid must have the flow grid's extents and slab");
+    return 0;
+}
+int wl_budget_update(wl_dtype t_flow, wl_dtype t_acc, const wl_grid *g, const void *u, const void *p, const wl_grid *ga, const void *Uf,
+                     const void *Pm, void *R, void *PU, void *GG, void *T3, double eps, int first) {
+    if (!g || !ga) return fail(WL_E_ARG, "wl_budget_update: null grid", __FILE__, __LINE__);
+    WL_TRY(check_grid(g));
+    WL_TRY(check_grid(ga));
+    WL_TRY(check_dtype("wl_budget_update", t_flow));
+    WL_TRY(check_dtype("wl_budget_update", t_acc));
+    if (t_flow == WL_F64 && t_acc == WL_F32)
+        return fail(WL_E_ARG, "wl_budget_update: Float32 accumulators on a Float64 flow", __FILE__, __LINE__);
+    if (!u || !p || !Uf || !Pm || !R || !PU || !GG || !T3)
+        return fail(WL_E_ARG, "wl_budget_update: null u, p, Uf, Pm, R, PU, GG or T3", __FILE__, __LINE__);
+    if (g->D != 2 && g->D != 3) return fail(WL_E_ARG, "wl_budget_update: D must be 2 or 3", __FILE__, __LINE__);
+    WL_TRY(check_acc_grid("wl_budget_update", g, ga));
+    if (!(eps > 0.0 && eps <= 1.0)) return fail(WL_E_ARG, "wl_budget_update: eps must lie in (0, 1]", __FILE__, __LINE__);
+    const G gf = mkG(g), gacc = mkG(ga);
+    WL_TRY(check_halo_planes("wl_budget_update", gf, true));
+#define WL_BUDGET(TF, TA, DD) op_budget_update<TF, TA, DD>(gf, gacc, (const TF *)u, (const TF *)p, (const TA *)Uf, (const TA *)Pm, (TA *)R, (TA *)PU, (TA *)GG, (TA *)T3, eps, first)
+    if (t_acc == WL_F64) WL_DISPATCH(t_flow, g->D, (WL_BUDGET(T, double, DD)));
+    if (g->D == 3) return WL_BUDGET(float, float, 3);
+    return WL_BUDGET(float, float, 2);
+#undef WL_BUDGET
+}
+int wl_budget_terms(wl_dtype t_acc, const wl_grid *ga, const void *Uf, const void *R, const void *PU, const void *GG, const void *T3,
+                    double nu, void *out) {
+    if (!ga) return fail(WL_E_ARG, "wl_budget_terms: null grid", __FILE__, __LINE__);
+    WL_TRY(check_grid(ga));
+    WL_TRY(check_dtype("wl_budget_terms", t_acc));
+    if (!Uf || !R || !PU || !GG || !T3 || !out) return fail(WL_E_ARG, "wl_budget_terms: null Uf, R, PU, GG, T3 or out", __FILE__, __LINE__);
+    if (ga->D != 2 && ga->D != 3) return fail(WL_E_ARG, "wl_budget_terms: D must be 2 or 3", __FILE__, __LINE__);
+    if (!std::isfinite(nu)) return fail(WL_E_ARG, "wl_budget_terms: nu must be finite", __FILE__, __LINE__);
+    const G gg = mkG(ga);
+    WL_TRY(check_halo_planes("wl_budget_terms", gg, true));
+    WL_DISPATCH(t_acc, ga->D, (op_budget_terms<T, DD>(gg, (const T *)Uf, (const T *)R, (const T *)PU, (const T *)GG, (const T *)T3, nu, (T *)out)));
 }
 int wl_interp(wl_dtype t, const wl_grid *g, const void *a, int ncomp, const double *x_dev, int64_t m, double *out_dev,
               int64_t ldo) {
