@@ -1005,7 +1005,11 @@ enum {
      * return (see wl_mom_step) (default), 0 = separate BDIM! pass, u0 = the copy of u */
     WL_OPT_BDIM_IN_CONVDIFF = 27,
     /* 1 = consecutive marching kernels sweep their tiles in opposite directions, each XCD starting on the lines the kernel
-     * before it touched last (L2 / Infinity Cache) (default), 0 = always ascending.  Same bits either way. */
+     * before it touched last (L2 / Infinity Cache) (default), 0 = always ascending.  Two bits: bit 0 is that switch; bit 1
+     * chooses which tiles an XCD takes in a z-marching launch: clear = whole z-chunks are dealt round-robin to the eight XCDs
+     * (the body's rows, which cost more, are spread over all of them), set = every XCD takes one contiguous slab of z.  So
+     * 1 (default) = alternate + dealt, 3 = alternate + slabs, 0 = ascending + dealt, 2 = ascending + slabs.  Same bits in all
+     * four: a tile's reduction partial keeps its slot. */
     WL_OPT_SWEEP_ALTERNATE = 30,
     /* 1 = inside the one-workgroup bottom of the V-cycle (levels of <= 4096 cells) pcg! keeps its level in registers and LDS
      * for the whole call (default), 0 = every phase goes through global memory.  Same bits either way. */
@@ -1034,6 +1038,8 @@ int wl_prof_counts(int kclass, int64_t *launches, int64_t *cells);
 int wl_prof_allocs(int64_t *count, int64_t *bytes);
 /* number of stencil launches since start-up that were split to overlap a z-slab halo exchange (comm stream) */
 int wl_prof_overlapped(int64_t *count);
+/* number of z-marching launches since start-up whose z-chunks were dealt round-robin to the XCDs (WL_OPT_SWEEP_ALTERNATE) */
+int wl_prof_dealt(int64_t *count);
 /* collectives issued by this rank since the last wl_prof_reset (z-slab runs; all zero without a communicator):
  * out[0] all-reduces, out[1] halo exchanges (one grouped send/recv batch each), out[2] send/recv pairs inside them (one per
  * component and neighbour side), out[3] all-gathers, out[4] bytes this rank sent in halo exchanges, out[5] bytes it

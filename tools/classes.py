@@ -23,7 +23,7 @@ sim = bench.sphere((size,) * 3, T)
 names = {L.wl_kernel_name(k).decode(): k for k in range(24)}
 for _ in range(int(os.environ.get('WL_PRESTEPS', '30'))):   # past the impulsive start: 1 V-cycle per solve
     S.sim_step(sim, remeasure=False)
-classes = ["pcg_mult_dot", "pcg_update", "pcg_direction", "pcg_init", "smooth", "residual", "conv_diff", "bdim", "correct", "div",
+classes = ["pcg_mult_dot", "pcg_update", "pcg_direction", "pcg_init", "smooth", "prolongate", "residual", "conv_diff", "bdim", "correct", "div",
            "scale", "cfl"]
 res = {}
 for r in range(reps):

@@ -88,7 +88,9 @@ WL_BODY_MAXLEAF = 6
 
 
 class Opt(enum.IntEnum):
-    """wl_set_option keys: the WL_OPT_* enumerators of include/wlhip.h (tests/test_options.py holds the two together)."""
+    """wl_set_option keys: the WL_OPT_* enumerators of include/wlhip.h (tests/test_options.py holds the two together).
+    SWEEP_ALTERNATE holds two bits: bit 0 = consecutive marching kernels sweep in opposite directions, bit 1 = every XCD keeps
+    one contiguous slab of z instead of z-chunks dealt round-robin (1: default, 3: alternate + slabs, 0 / 2: ascending)."""
     STENCIL7_VEC = 0
     SMOOTH_FUSED = 1
     CONVDIFF_TILED = 2
@@ -282,6 +284,7 @@ def lib() -> C.CDLL:
         "wl_prof_select": (i, [i, i64]),
         "wl_prof_reset": (i, []),
         "wl_prof_overlapped": (i, [C.POINTER(i64)]),
+        "wl_prof_dealt": (i, [C.POINTER(i64)]),
         "wl_prof_counts": (i, [i, C.POINTER(i64), C.POINTER(i64)]),
         "wl_prof_allocs": (i, [C.POINTER(i64), C.POINTER(i64)]),
         "wl_prof_comm": (i, [C.POINTER(i64)]),

@@ -263,7 +263,8 @@ __global__ __launch_bounds__(256) void k_budget_update(G g, G ga, BgPtr<T, A, D>
     }
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     int lb, pslot;
-    tile_of(blockIdx.x, nblk, 0, lb, pslot);
+    // (contiguous map, tpp = 0: every row of the budget update costs the same, body or not, so there is nothing to spread)
+    tile_of(blockIdx.x, nblk, 0, 0, lb, pslot);
     (void)pslot;
     const int ch = lb / tpp, pt = lb - ch * tpp;
     const int q = (pt % ntx) * 64 + lane;                             // vector index within the row

@@ -22,6 +22,7 @@
 
 #include "../../include/wlhip.h"
 #include "wl_buf.h"
+#include "wl_tilemap.h"
 
 namespace wl {
 
@@ -74,7 +75,8 @@ struct Mailbox {
 };
 
 // wl_set_option (names and meaning: include/wlhip.h): THE table of keys and defaults.  A key is live when it has a row;
-// the initial values of Ctx::opt and the mask wl_set_option checks are derived from it.
+// the initial values of Ctx::opt and the mask wl_set_option checks are derived from it.  WL_OPT_SWEEP_ALTERNATE holds two
+// bits (bit 0: alternate sweeps, bit 1: contiguous z slabs per XCD instead of dealt z-chunks; see sweep_rev / sweep_word).
 struct OptRow { int key, def; };
 constexpr OptRow WL_OPT_ROWS[] = {
     {WL_OPT_STENCIL7_VEC, 1},         {WL_OPT_SMOOTH_FUSED, 1},       {WL_OPT_CONVDIFF_TILED, 1},  {WL_OPT_BDIM_ROWFLAGS, 1},
@@ -112,6 +114,7 @@ struct Ctx {
     hipEvent_t ev_prod = nullptr, ev_halo = nullptr;
     bool halo_pending = false;
     int64_t n_overlapped = 0;          // stencil launches split around an exchange (wl_prof_overlapped)
+    int64_t n_dealt = 0;               // marching launches whose z-chunks were dealt round-robin to the XCDs (wl_prof_dealt)
     int64_t n_alloc = 0, alloc_bytes = 0;   // device + pinned-host allocations the library has made (wl_prof_allocs)
 };
 Ctx &ctx();
@@ -287,7 +290,9 @@ inline Tiling mk_tiling(const Range &R) {
 }
 inline int grid_for(const Tiling &t) { return t.nblk; }
 
-// logical block id: XCD x (= blockIdx % 8) receives the contiguous range [x*nblk/8, (x+1)*nblk/8)
+// logical block id: XCD x (= blockIdx % 8) receives the contiguous range [x*nblk/8, (x+1)*nblk/8).  (The generic range
+// kernels keep this map: their tiles are strided by ptb, not laid out chunk by chunk, every cell costs the same, and no
+// finest-level hot launch goes through them -- there is nothing for wl_tilemap.h's dealt map to spread.)
 __device__ inline int logical_block(int nblk) {
     const int b = blockIdx.x;
     return (nblk & 7) ? b : (b & 7) * (nblk >> 3) + (b >> 3);
@@ -695,24 +700,28 @@ inline int halo_end() {
     return 0;
 }
 
-// Consecutive marching kernels sweep in OPPOSITE directions (WL_OPT_SWEEP_ALTERNATE): each XCD keeps its range of tiles -- its slab
-// of the z axis, the same for every kernel -- but starts where the kernel before it stopped, on the lines that kernel has
+// Consecutive marching kernels sweep in OPPOSITE directions (WL_OPT_SWEEP_ALTERNATE, bit 0): each XCD keeps its list of tiles -- the
+// same z-chunks for every kernel of one shape -- but starts where the kernel before it stopped, on the lines that kernel has
 // just read or written and that still sit in the XCD's L2 and in the 256 MB Infinity Cache (a 512^3 Float32 array is
 // 537 MB: without the reversal every kernel begins on the lines that were evicted first).  The tile a workgroup takes
 // changes, the slot its reduction partial goes to stays that tile's: sums and fields are bit-identical either way.
 inline int sweep_rev() {
     Ctx &c = ctx();
-    if (!opt(WL_OPT_SWEEP_ALTERNATE)) return 0;
+    if (!(opt(WL_OPT_SWEEP_ALTERNATE) & 1)) return 0;
     c.sweep ^= 1;
     return c.sweep;
 }
-// logical tile of physical workgroup b, and the slot of that tile's partial (= the workgroup that takes it when rev = 0)
-__device__ __forceinline__ void tile_of(int b, int nblk, int rev, int &lb, int &pslot) {
-    if (nblk & 7) { lb = b; pslot = b; return; }
-    const int per = nblk >> 3, q = b >> 3;
-    const int qq = rev ? per - 1 - q : q;
-    lb = (b & 7) * per + qq;
-    pslot = (qq << 3) | (b & 7);
+// Which tiles an XCD's list holds (wl_tilemap.h): whole z-chunks dealt round-robin, or with bit 1 of WL_OPT_SWEEP_ALTERNATE
+// set one contiguous slab of z per XCD.  The launchers hand the kernels one "sweep word": bit 0 = walk the list backwards
+// (`rev`, from sweep_rev), bit 1 = keep the slabs; launches that really deal are counted (wl_prof_dealt).
+constexpr int WL_SWEEP_REV = 1, WL_SWEEP_SLABS = 2;
+inline int sweep_word(int rev, int nblk, int tpp) {
+    const bool slabs = (opt(WL_OPT_SWEEP_ALTERNATE) & 2) != 0;
+    if (!slabs && tilemap_dealt(nblk, tpp)) ctx().n_dealt += 1;
+    return (rev ? WL_SWEEP_REV : 0) | (slabs ? WL_SWEEP_SLABS : 0);
+}
+__device__ __forceinline__ void tile_of_sweep(int b, int nblk, int tpp, int sweep, int &lb, int &pslot) {
+    tile_of(b, nblk, (sweep & WL_SWEEP_SLABS) ? 0 : tpp, sweep & WL_SWEEP_REV, lb, pslot);
 }
 
 // ---- neighbour-lane exchange by DPP wave shifts (gfx9 family: wave_shr:1 / wave_shl:1): one VALU move per 32 bits,

@@ -108,7 +108,9 @@ __global__ __launch_bounds__(CD_BX *CD_BY) void k_convdiff3(G g, T *__restrict__
         if (q < segs.n && (int)blockIdx.x >= segs.s[q].b0) sg = segs.s[q];   // (scalar selects: uniform per workgroup)
     const int nblk = sg.nblk, tpp = sg.tpp, clen = sg.clen, ty0 = sg.ty0, ntile = sg.ntile, zlo = sg.zlo, zhi = sg.zhi;
     const int b = (int)blockIdx.x - sg.b0;
-    const int lb = (nblk & 7) ? b : (b & 7) * (nblk >> 3) + (b >> 3);  // XCD-contiguous logical id
+    // XCD-contiguous logical id.  (Stays contiguous: a launch is up to four small boxes of boundary tiles, each with its own
+    // chunking and first block, a few per cent of conv_diff!'s cells -- too few chunks per box to deal out.)
+    const int lb = (nblk & 7) ? b : (b & 7) * (nblk >> 3) + (b >> 3);
     const int ch = lb / tpp, pt = lb - ch * tpp;
     const int i0 = 1 + CD_BX * (pt % ntx), j0 = CD_BY * (ty0 + pt / ntx);   // ty0: first tile row of this segment
     const int n0 = g.n[0], n1 = g.n[1], n2 = g.n[2], nzg = g.nzg, kz0 = g.kz0;
@@ -516,7 +518,7 @@ __global__ __launch_bounds__(CD_BX *BY) void k_convdiff3s(G g, T *__restrict__ r
     CdsShared<T, BY> &S_ = *reinterpret_cast<CdsShared<T, BY> *>(cds_raw);
     const int b = blockIdx.x;
     int lb, pslot;
-    tile_of(b, nblk, rev, lb, pslot);                                  // XCD-contiguous logical id
+    tile_of_sweep(b, nblk, tpp, rev, lb, pslot);                       // (rev: the launcher's sweep word; wl_tilemap.h)
     (void)pslot;
     const int ch = lb / tpp, pt = lb - ch * tpp;
     const int n0 = g.n[0], n1 = g.n[1];
@@ -613,7 +615,7 @@ int launch_convdiff3(const G &g, T *r, const T *u, double nu_, const T *u0, T *u
         constexpr size_t lds = sizeof(CdsShared<T, BY>);
         static_assert(lds <= 64 * 1024, "conv_diff tile: more LDS than a launch gets without opting in");
         hipLaunchKernelGGL((k_convdiff3s<T, FUSE, COPY, BY, FIN>), dim3(nblk), dim3(CD_BX * BY), lds, ctx().stream, g, r, u, (T)nu_, u0, u0out, V,
-                           (T)dt_, a3[0], a3[1], a3[2], has_acc, ntx, tpp, nblk, clen, jbase, klo, khi, ntile, rev, fn);
+                           (T)dt_, a3[0], a3[1], a3[2], has_acc, ntx, tpp, nblk, clen, jbase, klo, khi, ntile, sweep_word(rev, nblk, tpp), fn);
         return (int)hipGetLastError();
     };
     const int rows = nty * CD_BY, jb0 = tlo * CD_BY;

@@ -850,7 +850,7 @@ __global__ __launch_bounds__(64 * S7_BY) void k_correct3(G g, T *__restrict__ u,
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int b = blockIdx.x;
     int lb, pslot;
-    tile_of(b, nblk, rev, lb, pslot);
+    tile_of_sweep(b, nblk, tpp, rev, lb, pslot);   // (rev: the launcher's sweep word)
     (void)pslot;
     const int ch = lb / tpp, pt = lb - ch * tpp;
     const int i = 1 + (pt % ntx) * 64 * V + lane * V, j = 1 + (pt / ntx) * S7_BY + wv;
@@ -928,7 +928,7 @@ int op_correct(const G &g, T *u, const T *L, const T *x, const T *rowc = nullptr
             Prof p(WL_K_CORRECT, R.count());
             const XBc<T> xb = (xbc && xbc->on) ? *xbc : XBc<T>{0, 0, (T)0};
             hipLaunchKernelGGL((k_correct3<T>), dim3(tpp * nchunk), dim3(64 * S7_BY), 0, ctx().stream, g, u, L, x, rowc, ntx, tpp,
-                               tpp * nchunk, clen, R.lo[2], R.hi[2], xb, sweep_rev());
+                               tpp * nchunk, clen, R.lo[2], R.hi[2], xb, sweep_word(sweep_rev(), tpp * nchunk, tpp));
             if (xdone) *xdone = xb.on != 0;
             return (int)hipGetLastError();
         }

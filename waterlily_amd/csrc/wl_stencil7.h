@@ -91,7 +91,7 @@ struct Gate {
     int f32 = 1;                    // the solver's element type is Float32 (scalars are rounded to it)
     int also_x = 0;                 // run also when only the deferred x update is owed (direction kernel)
     int inv = 0;                    // kind 0: the body runs when *active == 0 instead
-    int rev = 0;                    // every XCD walks its range of tiles backwards (set by the launchers, see sweep_rev)
+    int rev = 0;                    // sweep word (set by the launchers, see sweep_word): bit 0 = every XCD walks its tiles backwards, bit 1 = contiguous slabs
     int zcap = 0;                   // host side: > 0 = cut z into at most this many chunks (few partials for the consumer's sum)
 };
 // budget of per-workgroup partials a pcg! kernel may sum itself (Gate kind 1..3): the grid of the kernels of such a call is
@@ -269,7 +269,7 @@ __global__ __launch_bounds__(64 * S7_BY) void k_stencil7(G g, SRC src, const T *
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int b = blockIdx.x;
     int lb, pslot;
-    tile_of(b, nblk, gate.rev, lb, pslot);                             // XCD-contiguous logical id
+    tile_of_sweep(b, nblk, tpp, gate.rev, lb, pslot);                  // z-chunks dealt to the XCDs (wl_tilemap.h)
     const int ch = lb / tpp, pt = lb - ch * tpp;
     const int n0 = g.n[0], n1 = g.n[1], nxi = n0 - 2, nyi = n1 - 2;
     const int i = 1 + (pt % ntx) * 64 * V + lane * V;
@@ -460,7 +460,7 @@ __global__ __launch_bounds__(256) void k_rowvec(G g, LD ld, ST st, const T *rowc
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int b = blockIdx.x;
     int lb, pslot;
-    tile_of(b, nblk, gate.rev, lb, pslot);
+    tile_of_sweep(b, nblk, tpp, gate.rev, lb, pslot);
     const int ch = lb / tpp, pt = lb - ch * tpp;
     const int i = 1 + (pt % ntx) * 64 * V + lane * V;
     const int j = __builtin_amdgcn_readfirstlane(1 + (pt / ntx) * 4 + wv);
@@ -539,7 +539,7 @@ inline int launch_rowvec(int kclass, const G &g, LD ld, ST st, const T *rowc, do
     if (nblk > WL_MAXB) return -1;
     if (np) *np = nblk;
     Prof p(kclass, R.count());
-    gate.rev = sweep_rev();
+    gate.rev = sweep_word(sweep_rev(), nblk, tpp);
     hipLaunchKernelGGL((k_rowvec<T, NRED, RK, LD, ST, OP>), dim3(nblk), dim3(256), 0, ctx().stream, g, ld, st, RK ? rowc : nullptr, partials,
                        ntx, tpp, nblk, clen, R.lo[2], R.hi[2], gate);
     return (int)hipGetLastError();
@@ -621,7 +621,7 @@ inline int launch_stencil7_r(int kclass, const G &g, SRC src, const T *L, const 
     if (nblk > WL_MAXB) return -1;   // plane too large for the partial buffer: caller falls back
     if (np) *np = nblk;
     Prof p(kclass, Rg.count());
-    gate.rev = sweep_rev();
+    gate.rev = sweep_word(sweep_rev(), nblk, tpp);
     hipLaunchKernelGGL((k_stencil7<T, NRED, R, SRC, EPI>), dim3(nblk), dim3(64 * S7_BY), 0, ctx().stream, g, src, L, rowc, ea, eb, epi,
                        partials, ntx, tpp, nblk, clen, klo, khi, gate);
     return (int)hipGetLastError();
