@@ -52,22 +52,24 @@ class MeshPose(C.Structure):
                 ("Ainv", C.c_double * 9), ("identity_map", C.c_int32)]
 
 
+# how wl_hist_axis, wl_tp_value and wl_rg_value (include/wlhip.h) all begin: the field and which value of a cell is formed from it
+_VALUE_FIELDS = [("f", C.c_void_p), ("kind", C.c_int32), ("ipar", C.c_int32), ("par", C.c_double * 3), ("par2", C.c_double * 3)]
+
+
 class HistAxis(C.Structure):
     """wl_hist_axis (include/wlhip.h): one axis of a histogram"""
-    _fields_ = [("f", C.c_void_p), ("kind", C.c_int32), ("ipar", C.c_int32), ("par", C.c_double * 3), ("par2", C.c_double * 3),
-                ("absval", C.c_int32), ("nbins", C.c_int32), ("lo", C.c_double), ("hi", C.c_double), ("range_dev", C.c_void_p),
-                ("edges_dev", C.c_void_p)]
+    _fields_ = _VALUE_FIELDS + [("absval", C.c_int32), ("nbins", C.c_int32), ("lo", C.c_double), ("hi", C.c_double),
+                                ("range_dev", C.c_void_p), ("edges_dev", C.c_void_p)]
 
 
 class TpValue(C.Structure):
     """wl_tp_value (include/wlhip.h): one of the two values of a two-point statistic"""
-    _fields_ = [("f", C.c_void_p), ("kind", C.c_int32), ("ipar", C.c_int32), ("par", C.c_double * 3), ("par2", C.c_double * 3)]
+    _fields_ = _VALUE_FIELDS
 
 
 class RgValue(C.Structure):
     """wl_rg_value (include/wlhip.h): the value whose threshold set wl_regions labels"""
-    _fields_ = [("f", C.c_void_p), ("kind", C.c_int32), ("ipar", C.c_int32), ("par", C.c_double * 3), ("par2", C.c_double * 3),
-                ("absval", C.c_int32)]
+    _fields_ = _VALUE_FIELDS + [("absval", C.c_int32)]
 
 
 WL_RG_BELOW, WL_RG_ABOVE = 0, 1

@@ -1,5 +1,6 @@
 """What the recorders beside the stepper share (Probes, Integrals, Forces; SurfaceLoads for the ranks alone): a Float64 buffer of
-rows that grows, the host list of the times, the flow the recorder was made for, and the ranks' parts of a z-slab run at the host.
+rows that grows, the host list of the times, the flow the recorder was made for, and the ranks' parts of a z-slab run at the host
+(the read-outs' gather() functions start from them too).
 Works on any torch device.
 """
 from __future__ import annotations
@@ -18,6 +19,13 @@ def _rank_parts(v: np.ndarray, slab) -> list:
     parts = [None] * slab.size
     dist.all_gather_object(parts, v)
     return parts
+
+
+def host_parts(x, slab) -> Tuple[list, bool]:
+    """How every gather() of a read-out starts: (the ranks' host copies of the tensor or array x in rank order, whether this
+    rank is the one that returns the result: rank 0, or the only one).  Every rank must call it."""
+    v = x.detach().cpu().numpy().copy() if isinstance(x, torch.Tensor) else np.asarray(x)
+    return _rank_parts(v, slab), slab is None or slab.size == 1 or slab.rank == 0
 
 
 def _add(parts: list) -> np.ndarray:

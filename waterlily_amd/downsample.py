@@ -29,42 +29,22 @@ import numpy as np
 import torch
 
 from . import _lib
-from . import render
+from . import _readout as R
+from . import _series
 from . import sim as S
 from . import vtk
 from ._lib import check
+from ._readout import R_FACE  # noqa: F401  (the kind's number, under this module's name too)
 
-R_FACE = 3
 FACTORS = (1, 2, 4, 8, 16)
-_MODE = dict(render._MODE, sample=5)
-_KIND = dict(render._KIND, face=R_FACE)
-
-
-class _DevBuf:
-    """A block of device memory from the library's allocator (wl_malloc: counted by wl_prof_allocs), freed with the object.
-    torch views it through __cuda_array_interface__ and keeps the object alive for as long as a view exists."""
-
-    def __init__(self, nbytes: int):
-        self.nbytes = max(1, int(nbytes))
-        p = C.c_void_p()
-        check(_lib.lib().wl_malloc(C.byref(p), C.c_size_t(self.nbytes)))
-        self.ptr = p.value
-        check(_lib.lib().wl_memset0(C.c_void_p(self.ptr), C.c_size_t(self.nbytes)))
-        self.__cuda_array_interface__ = {"shape": (self.nbytes,), "typestr": "|u1", "data": (self.ptr, False), "version": 2}
-
-    def tensor(self, dtype, device) -> torch.Tensor:
-        return torch.as_tensor(self, device=device).view(dtype)
-
-    def __del__(self):
-        if getattr(self, "ptr", None):
-            _lib.lib().wl_free(C.c_void_p(self.ptr))
-            self.ptr = None
+_MODE = dict(R.MODE, sample=5)
+_KIND = dict(R.KIND, face=R_FACE)
 
 
 def extent(g, factor: int, lo, hi) -> Tuple[Tuple[int, int, int], int]:
     """wl_downsample_extent: (this rank's coarse extents (ncx, ncy, ncz), its first coarse plane) for the grid g and the box"""
     nc, k0 = (C.c_int32 * 3)(), C.c_int32()
-    check(_lib.lib().wl_downsample_extent(C.byref(g), int(factor), render._i3(lo), render._i3(hi), nc, C.byref(k0)))
+    check(_lib.lib().wl_downsample_extent(C.byref(g), int(factor), R.i3(lo), R.i3(hi), nc, C.byref(k0)))
     return (int(nc[0]), int(nc[1]), int(nc[2])), int(k0.value)
 
 
@@ -72,14 +52,13 @@ def trim(N, factor: int, box=None):
     """The box (lo, hi) -- default: inside() of arrays of extents N -- with its high side cut down to extents that are multiples
     of `factor`."""
     D, f = len(N), int(factor)
-    lo = [1] * D if box is None else [int(x) for x in box[0]]
-    hi = [n - 1 for n in N] if box is None else [int(x) for x in box[1]]
+    lo, hi = R.inside(N) if box is None else R.sides(box)
     if len(lo) != D or len(hi) != D:
         raise ValueError(f"Downsampler: a box is (lo, hi) with {D} entries each")
-    hi = [l + (h - l) // f * f for l, h in zip(lo, hi)]
-    if any(not (0 <= l < h <= n - 1) for l, h, n in zip(lo, hi, N)):
-        raise ValueError(f"Downsampler: bad box: after trimming to multiples of {f} it must hold 0 <= lo < hi <= n - 1, got {lo}, {hi}")
-    return tuple(lo), tuple(hi)
+    hi = tuple(l + (h - l) // f * f for l, h in zip(lo, hi))
+    if not R.box_ok(lo, hi, N):
+        raise ValueError(f"Downsampler: bad box: after trimming to multiples of {f} it must hold 0 <= lo < hi <= n - 1, got {list(lo)}, {list(hi)}")
+    return lo, hi
 
 
 class Downsampler:
@@ -103,15 +82,14 @@ class Downsampler:
         lo, hi = self.box
         self.vbox = (lo, tuple(h + self.factor if h + self.factor <= n - 1 else h for h, n in zip(hi, N)))
         self.vnc, self.vk0 = extent(g, self.factor, *self.vbox)
-        self._vol = _DevBuf(int(np.prod(self.nc)) * self.T.itemsize)
-        self._vel: Optional[_DevBuf] = None
+        self._vol = R.DevBuf(int(np.prod(self.nc)) * self.T.itemsize)
+        self._vel: Optional[R.DevBuf] = None
 
 
 def _call(d: Downsampler, f: torch.Tensor, k: int, m: int, i: int, par, par2, box, ptr: int, ntuple: int, c: int) -> None:
-    g = render._field_grid(d.flow, f, k != render.R_SCALAR, "Downsampler")
-    check(_lib.lib().wl_downsample(S._WLT[S._T(f)], C.byref(g), S._ptr(f), k, int(i), None if par is None else _lib.d3(par),
-                                   None if par2 is None else _lib.d3(par2), m, d.factor, render._i3(box[0]), render._i3(box[1]), S._WLT[d.T],
-                                   C.c_void_p(ptr), int(ntuple), int(c)))
+    g = R.field_grid(d.flow, f, k != R.R_SCALAR, "Downsampler")
+    check(_lib.lib().wl_downsample(S._WLT[S._T(f)], C.byref(g), S._ptr(f), *R.Value(k, i, par, par2).flat(), m, d.factor, R.i3(box[0]),
+                                   R.i3(box[1]), S._WLT[d.T], C.c_void_p(ptr), int(ntuple), int(c)))
 
 
 def volume(d: Downsampler, f: torch.Tensor, kind="scalar", mode: str = "mean", i: int = 0, par=None, par2=None) -> torch.Tensor:
@@ -120,7 +98,7 @@ def volume(d: Downsampler, f: torch.Tensor, kind="scalar", mode: str = "mean", i
     cell centre / the fine faces on the block's low i-face), or a metric of f = u: "ke", "curl", "omega_mag", "omega_theta",
     "lambda2" (i, par, par2 as waterlily_amd.sim.metric).  mode: "mean", "sum", "max", "min", "absmax" (the signed value of
     largest magnitude), "sample" (the block's first cell).  On a z-slab the view holds this rank's coarse planes."""
-    _call(d, f, render._code(_KIND, kind), render._code(_MODE, mode), i, par, par2, d.box, d._vol.ptr, 1, 0)
+    _call(d, f, R.code(_KIND, kind), R.code(_MODE, mode), i, par, par2, d.box, d._vol.ptr, 1, 0)
     nc = d.nc
     t = d._vol.tensor(S._TORCH[d.T], d.flow.device)[:nc[0] * nc[1] * nc[2]]
     return t.view(nc[1], nc[0]).permute(1, 0) if d.D == 2 else t.view(nc[2], nc[1], nc[0]).permute(2, 1, 0)
@@ -132,7 +110,7 @@ def velocity(d: Downsampler, u: torch.Tensor) -> torch.Tensor:
     factor^(1-D) times the sum of the fine div over the block: every interior fine face cancels."""
     nc, D = d.vnc, d.D
     if d._vel is None:
-        d._vel = _DevBuf(int(np.prod(nc)) * D * d.T.itemsize)
+        d._vel = R.DevBuf(int(np.prod(nc)) * D * d.T.itemsize)
     for c in range(D):
         _call(d, u, R_FACE, _MODE["mean"], c, None, None, d.vbox, d._vel.ptr, D, c)
     t = d._vel.tensor(S._TORCH[d.T], d.flow.device)[:nc[0] * nc[1] * nc[2] * D]
@@ -143,15 +121,10 @@ def gather(part, slab=None):
     """The ranks' parts of one volume() or velocity() on rank 0 as a host array (None on the other ranks; every rank must call
     it): the parts concatenated along z in rank order, which is the undecomposed volume bit for bit, since no block straddles
     two ranks."""
-    h = part.detach().cpu().numpy().copy() if isinstance(part, torch.Tensor) else np.asarray(part)
-    if slab is None or slab.size == 1:
-        return h
-    import torch.distributed as dist
-    parts = [None] * slab.size
-    dist.all_gather_object(parts, h)
-    if slab.rank != 0:
+    parts, root = _series.host_parts(part, slab)
+    if not root:
         return None
-    return np.concatenate(parts, axis=2)
+    return parts[0] if len(parts) == 1 else np.concatenate(parts, axis=2)            # (a 2-D volume has no axis 2, and no ranks)
 
 
 # --------------------------------------------------------------------------- snapshots
@@ -212,8 +185,8 @@ def _plan(w: DownsampleWriter, sim):
         a = func(sim)
         if not isinstance(a, torch.Tensor) or not a.is_cuda:
             raise TypeError(f"attribute {name!r}: the function must return a device field of the simulation (e.g. sim.flow.u)")
-        k, m = render._code(_KIND, kind), render._code(_MODE, mode)
-        vec = a.ndim > D and k in (render.R_UCOMP, render.R_CENTRE, R_FACE)
+        k, m = R.code(_KIND, kind), R.code(_MODE, mode)
+        vec = a.ndim > D and k in (R.R_UCOMP, R.R_CENTRE, R_FACE)
         nct = 3 if vec else 1                                   # vectors carry 3 components (2-D: a zero third one)
         n = nc[0] * nc[1] * nc[2] * nct * tsz
         fields.append((name, a, k, m, vec, nct, nbytes, n))

@@ -33,24 +33,23 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import _readout as R
 from . import _series
-from . import render
 from . import sim as S
 from ._lib import check
-from .downsample import _DevBuf
 
 MAX_BINS, MAX_EDGES = 8192, 1024
 
 
-class Axis:
-    """One axis of a histogram.  kind: "scalar" (a scalar field), "ucomp" / "centre" (component i of a vector field, as stored /
-    averaged to the cell centre) or a metric of u: "ke", "curl", "omega_mag", "omega_theta", "lambda2" (i, par, par2 as
-    waterlily_amd.sim.metric).  abs: count |v|.  The bins, one of: range=(lo, hi) with `bins` uniform bins (finite, hi > lo);
-    range=None: `bins` uniform bins over the extremes of the field, found on the device by every non-accumulating count();
-    edges: bins + 1 strictly increasing finite numbers (at most 1024 bins), the last one closed as in numpy."""
+class Axis(R.Value):
+    """One axis of a histogram: a Value (kind, i, par, par2 as there) with bins.  abs: count |v| (.absval is the same).  The bins,
+    one of: range=(lo, hi) with `bins` uniform bins (finite, hi > lo); range=None: `bins` uniform bins over the extremes of the
+    field, found on the device by every non-accumulating count(); edges: bins + 1 strictly increasing finite numbers (at most
+    1024 bins), the last one closed as in numpy."""
 
     def __init__(self, kind="scalar", i: int = 0, par=None, par2=None, bins: int = 256, range=None, edges=None, abs: bool = False):
-        self.kind, self.i, self.par, self.par2, self.abs = render._code(render._KIND, kind), int(i), par, par2, bool(abs)
+        super().__init__(kind, i, par, par2, absval=abs)
+        self.abs = self.absval
         self.edges = None
         self.range = None
         if edges is not None:
@@ -87,31 +86,24 @@ class Histogram:
         sl = flow.layout.slab
         if sl is not None and sl.size > 1 and any(x is not None and x.auto for x in (a, b)):
             raise ValueError("Histogram: an automatic range is found per rank; on a decomposed flow give range=(lo, hi) or edges")
-        N = tuple(int(x) for x in flow.N)
-        self.box = None
-        if box is not None:
-            lo, hi = tuple(int(x) for x in box[0]), tuple(int(x) for x in box[1])
-            if len(lo) != self.D or len(hi) != self.D or any(not (0 <= l < h <= n - 1) for l, h, n in zip(lo, hi, N)):
-                raise ValueError(f"Histogram: a box is (lo, hi) with {self.D} entries each, 0 <= lo < hi <= n - 1")
-            self.box = (lo, hi)
+        box, given = R.box_of("Histogram", tuple(int(x) for x in flow.N), box)
+        self.box = box if given else None
         self._grid = flow.layout.grid()
         nb = C.c_int64()
         check(_lib.lib().wl_field_range_scratch(C.byref(self._grid), C.byref(nb)))
-        self._scratch = _DevBuf(nb.value)
-        self._cnt = _DevBuf(8 * (2 + self.A * self.B))
-        self._rng = _DevBuf(8 * 8)                               # a: doubles 0..3, b: 4..7
+        self._scratch = R.DevBuf(nb.value)
+        self._cnt = R.DevBuf(8 * (2 + self.A * self.B))
+        self._rng = R.DevBuf(8 * 8)                              # a: doubles 0..3, b: 4..7
         self._edges = {}
         for name, x in (("a", a), ("b", b)):
             if x is not None and x.edges is not None:
-                self._edges[name] = _DevBuf(8 * x.edges.size)
+                self._edges[name] = R.DevBuf(8 * x.edges.size)
                 self._edges[name].tensor(torch.float64, flow.device)[:x.edges.size].copy_(torch.from_numpy(x.edges))
         self._ax = {name: self._axis(name, x) for name, x in (("a", a), ("b", b)) if x is not None}
 
     def _axis(self, name: str, x: Axis) -> _lib.HistAxis:
-        s = _lib.HistAxis()
-        s.kind, s.ipar, s.absval, s.nbins = x.kind, x.i, int(x.abs), x.bins
-        s.par[:] = list(_lib.d3((0, 0, 0) if x.par is None else x.par))
-        s.par2[:] = list(_lib.d3((0, 0, 0) if x.par2 is None else x.par2))
+        s = x.fill(_lib.HistAxis())
+        s.nbins = x.bins
         if x.range is not None:
             s.lo, s.hi = x.range
         if x.auto:
@@ -120,13 +112,9 @@ class Histogram:
             s.edges_dev = self._edges[name].ptr
         return s
 
-    def _box(self):
-        return (None, None) if self.box is None else (render._i3(self.box[0]), render._i3(self.box[1]))
 
-
-def _field(h: Histogram, f: torch.Tensor, x: Axis) -> torch.Tensor:
-    render._field_grid(h.flow, f, x.kind != render.R_SCALAR, "Histogram")
-    return f
+def _field(h: Histogram, f: torch.Tensor, x: Axis) -> None:
+    R.field_grid(h.flow, f, x.kind != R.R_SCALAR, "Histogram")
 
 
 def range(h: Histogram, f: torch.Tensor, axis: str = "a") -> torch.Tensor:  # (hist.range; nothing below needs the builtin)
@@ -134,10 +122,9 @@ def range(h: Histogram, f: torch.Tensor, axis: str = "a") -> torch.Tensor:  # (h
     NaN cells -- in the object's buffer (NaN is skipped, -0 < +0, a box of nothing but NaN gives NaN, NaN)."""
     x = h.a if axis == "a" else h.b
     _field(h, f, x)
-    lo, hi = h._box()
+    lo, hi = R.box_args(h.box)
     out = h._rng.ptr + (0 if axis == "a" else 32)
-    check(_lib.lib().wl_field_range(S._WLT[S._T(f)], C.byref(h._grid), S._ptr(f), x.kind, x.i, None if x.par is None else _lib.d3(x.par),
-                                    None if x.par2 is None else _lib.d3(x.par2), int(x.abs), lo, hi, C.c_void_p(h._scratch.ptr),
+    check(_lib.lib().wl_field_range(S._WLT[S._T(f)], C.byref(h._grid), S._ptr(f), *x.flat(), int(x.absval), lo, hi, C.c_void_p(h._scratch.ptr),
                                     h._scratch.nbytes, C.c_void_p(out)))
     k = 0 if axis == "a" else 4
     return h._rng.tensor(torch.float64, h.flow.device)[k:k + 4]
@@ -159,7 +146,7 @@ def count(h: Histogram, fa: torch.Tensor, fb: Optional[torch.Tensor] = None, acc
         h._ax[name].f = f.data_ptr()
         if x.auto and not accumulate:
             range(h, f, name)
-    lo, hi = h._box()
+    lo, hi = R.box_args(h.box)
     check(_lib.lib().wl_histogram(S._WLT[S._T(fa)], C.byref(h._grid), C.byref(h._ax["a"]), C.byref(h._ax["b"]) if h.b is not None else None,
                                   lo, hi, int(bool(accumulate)), C.c_void_p(h._cnt.ptr)))
     return _view(h)
@@ -274,8 +261,5 @@ def combine(parts) -> np.ndarray:
 
 def gather(cnt, slab=None):
     """The ranks' counts added on rank 0 as a host array (None on the other ranks; every rank must call it)."""
-    v = cnt.detach().cpu().numpy().copy() if isinstance(cnt, torch.Tensor) else np.asarray(cnt)
-    parts = _series._rank_parts(v, slab)
-    if slab is not None and slab.size > 1 and slab.rank != 0:
-        return None
-    return combine(parts)
+    parts, root = _series.host_parts(cnt, slab)
+    return combine(parts) if root else None

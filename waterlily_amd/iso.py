@@ -26,9 +26,11 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import _readout as R
+from . import _series
 from . import sim as S
 from ._lib import check
-from .surface import _data_array
+from .vtk import data_array
 
 
 class Isosurface:
@@ -57,22 +59,14 @@ class Isosurface:
             self.val = torch.empty((self.capacity, 3), dtype=torch.float64, device=self.flow.device)
 
 
-def _box(box):
-    if box is None:
-        return None, None
-    lo, hi = box
-    return (C.c_int32 * 3)(*[int(x) for x in lo]), (C.c_int32 * 3)(*[int(x) for x in hi])
-
-
 def _check_field(isf: Isosurface, a: torch.Tensor, what: str) -> None:
-    p = isf.flow.p
-    if tuple(a.shape) != tuple(p.shape) or a.stride() != p.stride() or a.dtype != p.dtype:
+    if not R.laid_out_like(a, isf.flow.p):
         raise ValueError(f"Isosurface: {what} must be a scalar field with the layout of flow.p (use waterlily_amd.sim.like)")
 
 
 def _run(isf: Isosurface, a: torch.Tensor, c: float, color, box, cap: int) -> Tuple[int, int]:
     """one wl_isosurface call and the read of its count (the one synchronisation): (total, written)"""
-    lo, hi = _box(box)
+    lo, hi = R.box_args(box)
     g = S._grid_of(a, 3)
     check(_lib.lib().wl_isosurface(S._WLT[S._T(a)], C.byref(g), S._ptr(a), None if color is None else S._ptr(color), float(c), lo, hi,
                                    S._ptr(isf.tri) if cap else None, S._ptr(isf.val) if (cap and color is not None) else None,
@@ -99,7 +93,7 @@ def extract(isf: Isosurface, a: torch.Tensor, c: float, color: Optional[torch.Te
 def count(isf: Isosurface, a: torch.Tensor, c: float, box=None) -> int:
     """the number of triangles extract would return (on z-slabs: this rank's); nothing is written"""
     _check_field(isf, a, "the field")
-    lo, hi = _box(box)
+    lo, hi = R.box_args(box)
     g = S._grid_of(a, 3)
     check(_lib.lib().wl_isosurface(S._WLT[S._T(a)], C.byref(g), S._ptr(a), None, float(c), lo, hi, None, None, 0, S._ptr(isf.cnt)))
     return int(isf.cnt[0].item())
@@ -170,26 +164,20 @@ def write_vtp(path, tri, val=None, name: str = "color") -> None:
         v = val.detach().cpu().numpy() if isinstance(val, torch.Tensor) else np.asarray(val)
         pv = np.zeros(len(pts), dtype=np.float64)
         pv[conn.ravel()] = np.asarray(v, dtype=np.float64).ravel()          # equal vertices carry equal values
-        point_data = f'<PointData Scalars="{name}">\n' + _data_array(name, pv.astype(np.float32), "Float32") + "</PointData>\n"
+        point_data = f'<PointData Scalars="{name}">\n' + data_array(name, pv.astype(np.float32), "Float32") + "</PointData>\n"
     with open(path, "w") as o:
         o.write('<?xml version="1.0"?>\n<VTKFile type="PolyData" version="1.0" byte_order="LittleEndian">\n<PolyData>\n'
                 f'<Piece NumberOfPoints="{len(pts)}" NumberOfVerts="0" NumberOfLines="0" NumberOfStrips="0" NumberOfPolys="{nt}">\n'
-                "<Points>\n" + _data_array("Points", pts.astype(np.float32), "Float32") + "</Points>\n" + point_data
-                + "<Polys>\n" + _data_array("connectivity", conn.ravel(), "Int64") + _data_array("offsets", 3 * np.arange(1, nt + 1), "Int64")
+                "<Points>\n" + data_array("Points", pts.astype(np.float32), "Float32") + "</Points>\n" + point_data
+                + "<Polys>\n" + data_array("connectivity", conn.ravel(), "Int64") + data_array("offsets", 3 * np.arange(1, nt + 1), "Int64")
                 + "</Polys>\n</Piece>\n</PolyData>\n</VTKFile>\n")
 
 
 def gather(tri, val=None, slab=None):
     """The ranks' parts concatenated in rank order on rank 0 as numpy arrays (tri, val); (None, None) on the other ranks.  Every
     rank of a slab run must call it; without a slab it is a copy to the host."""
-    to_np = lambda x: None if x is None else (x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x))
-    t, v = to_np(tri), to_np(val)
-    if slab is None or slab.size == 1:
-        return t, v
-    import torch.distributed as dist
-    parts = [None] * slab.size
-    dist.all_gather_object(parts, (t, v))
-    if slab.rank != 0:
+    t, root = _series.host_parts(tri, slab)
+    v = None if val is None else _series.host_parts(val, slab)[0]                        # (val is None on every rank or on none)
+    if not root:
         return None, None
-    return (np.concatenate([p[0] for p in parts], axis=0),
-            None if v is None else np.concatenate([p[1] for p in parts], axis=0))
+    return np.concatenate(t, axis=0), None if v is None else np.concatenate(v, axis=0)

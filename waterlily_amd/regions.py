@@ -37,12 +37,11 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import _readout as R
 from . import _series
-from . import render
 from . import sim as S
 from ._lib import check
-from .downsample import _DevBuf
-from .twopoint import Value
+from ._readout import Value
 
 COLS = 13
 
@@ -79,15 +78,9 @@ class Regions:
         sl = flow.layout.slab
         if sl is not None and sl.size > 1:
             raise ValueError("Regions: a decomposed flow: regions cross ranks (merging rank-boundary labels is not there yet)")
-        N = tuple(int(x) for x in flow.N)
-        self.box = None
-        lo, hi = (1,) * self.D, tuple(n - 1 for n in N)
-        if box is not None:
-            lo, hi = tuple(int(x) for x in box[0]), tuple(int(x) for x in box[1])
-            if len(lo) != self.D or len(hi) != self.D or any(not (0 <= l < h <= n - 1) for l, h, n in zip(lo, hi, N)):
-                raise ValueError(f"Regions: a box is (lo, hi) with {self.D} entries each, 0 <= lo < hi <= n - 1")
-            self.box = (lo, hi)
-        if value.kind >= render.R_METRIC and min(lo) < 1:
+        (lo, hi), given = R.box_of("Regions", tuple(int(x) for x in flow.N), box)
+        self.box = (lo, hi) if given else None
+        if value.kind >= R.R_METRIC and min(lo) < 1:
             raise ValueError("Regions: the box of a metric kind must lie in inside()")
         self.lo, self.n = lo, tuple(h - l for l, h in zip(lo, hi))
         self.ncell = int(np.prod(self.n, dtype=np.int64))
@@ -100,25 +93,19 @@ class Regions:
         if int(capacity) < 0:
             raise ValueError("Regions: capacity must be >= 0")
         self._grid = flow.layout.grid()
-        self._val = _lib.RgValue()
-        self._val.kind, self._val.ipar, self._val.absval = value.kind, value.i, int(getattr(value, "absval", False))
-        self._val.par[:] = list(_lib.d3((0, 0, 0) if value.par is None else value.par))
-        self._val.par2[:] = list(_lib.d3((0, 0, 0) if value.par2 is None else value.par2))
+        self._val = value.fill(_lib.RgValue())
         nb = C.c_int64()
-        blo, bhi = self._box()
+        blo, bhi = R.box_args(self.box)
         check(_lib.lib().wl_regions_scratch(C.byref(self._grid), blo, bhi, C.byref(nb)))
-        self._scratch = _DevBuf(nb.value)
-        self._lab = _DevBuf(4 * self.ncell)
-        self._n = _DevBuf(8 * 4)
+        self._scratch = R.DevBuf(nb.value)
+        self._lab = R.DevBuf(4 * self.ncell)
+        self._n = R.DevBuf(8 * 4)
         self._tables(int(capacity))
 
     def _tables(self, capacity: int) -> None:
         self.capacity = capacity
-        self._tab = _DevBuf(8 * COLS * capacity) if capacity else None
-        self._ext = _DevBuf(8 * 2 * capacity) if capacity else None
-
-    def _box(self):
-        return (None, None) if self.box is None else (render._i3(self.box[0]), render._i3(self.box[1]))
+        self._tab = R.DevBuf(8 * COLS * capacity) if capacity else None
+        self._ext = R.DevBuf(8 * 2 * capacity) if capacity else None
 
 
 def _level(c) -> float:
@@ -133,9 +120,9 @@ def label(rg: Regions, field: torch.Tensor, c=None) -> Result:
     the rows >= count mean nothing.  c: another level for this call.  No synchronisation."""
     if S._T(field) != np.dtype(rg.flow.T):
         raise ValueError("Regions: the field must have the flow's dtype")
-    render._field_grid(rg.flow, field, rg.value.kind != render.R_SCALAR, "Regions")
+    R.field_grid(rg.flow, field, rg.value.kind != R.R_SCALAR, "Regions")
     rg._val.f = field.data_ptr()
-    lo, hi = rg._box()
+    lo, hi = R.box_args(rg.box)
     cap = rg.capacity
     check(_lib.lib().wl_regions(S._WLT[S._T(field)], C.byref(rg._grid), C.byref(rg._val), rg.cmp, rg.c if c is None else _level(c),
                                 rg.periodic_mask, lo, hi, C.c_void_p(rg._lab.ptr), cap, C.c_void_p(rg._tab.ptr) if cap else None,
@@ -273,8 +260,8 @@ class _SumBufs:
     def __init__(self, capacity: int):
         n = _lib.WL_RS_MAX_COLS
         self.capacity = capacity
-        self.acc, self.val = _DevBuf(8 * 5 * n * capacity), _DevBuf(8 * n * capacity)
-        self.scale, self.over = _DevBuf(4 * n), _DevBuf(8 * n)
+        self.acc, self.val = R.DevBuf(8 * 5 * n * capacity), R.DevBuf(8 * n * capacity)
+        self.scale, self.over = R.DevBuf(4 * n), R.DevBuf(8 * n)
         self.cols = (_lib.RsCol * n)()
 
 
@@ -306,7 +293,7 @@ def sums(rg: Regions, res: Result, weights: Sequence, field: Optional[torch.Tens
     while len(bufs) < len(chunks):
         bufs.append(_SumBufs(cap))
     rg._sums = bufs
-    lo, hi = rg._box()
+    lo, hi = R.box_args(rg.box)
     parts = []
     for k, (ch, b) in enumerate(zip(chunks, bufs)):
         for c, w in enumerate(ch):
@@ -315,11 +302,9 @@ def sums(rg: Regions, res: Result, weights: Sequence, field: Optional[torch.Tens
                 raise ValueError("Regions: a weight without a field, and no field given to sums")
             if S._T(f) != T:
                 raise ValueError("Regions: the field must have the flow's dtype")
-            render._field_grid(rg.flow, f, w.value.kind != render.R_SCALAR, "Regions")
+            R.field_grid(rg.flow, f, w.value.kind != R.R_SCALAR, "Regions")
             col = b.cols[c]
-            col.v.f, col.v.kind, col.v.ipar, col.v.absval = f.data_ptr(), w.value.kind, w.value.i, int(getattr(w.value, "absval", False))
-            col.v.par[:] = list(_lib.d3((0, 0, 0) if w.value.par is None else w.value.par))
-            col.v.par2[:] = list(_lib.d3((0, 0, 0) if w.value.par2 is None else w.value.par2))
+            w.value.fill(col.v).f = f.data_ptr()
             col.power, col.moment = w.power, -1 if w.moment is None else w.moment
         nc = len(ch)
         sc = b.scale.tensor(torch.int32, dev)[:nc]
@@ -491,6 +476,6 @@ def lambda2(rg: Regions, sim, c=None) -> Result:
     Value("lambda2") and below=...; c: another level for this call (hist.quantile picks one)."""
     if sim.flow is not rg.flow:
         raise ValueError("Regions: the simulation's flow differs from the one the object was made for")
-    if rg.value.kind != render._KIND["lambda2"] or rg.cmp != _lib.WL_RG_BELOW:
+    if rg.value.kind != R.KIND["lambda2"] or rg.cmp != _lib.WL_RG_BELOW:
         raise ValueError('Regions: lambda2 needs Regions(flow, Value("lambda2"), below=c)')
     return table(rg, sim.flow.u, c)

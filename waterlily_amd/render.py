@@ -30,13 +30,11 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import _readout as R
+from . import _series
 from . import sim as S
 from ._lib import check
-
-R_SCALAR, R_UCOMP, R_CENTRE, R_METRIC = 0, 1, 2, 16
-_MODE = {"max": 0, "min": 1, "absmax": 2, "sum": 3, "mean": 4}
-_KIND = {"scalar": R_SCALAR, "ucomp": R_UCOMP, "centre": R_CENTRE, "center": R_CENTRE}
-_KIND.update({k: R_METRIC + v for k, v in S._METRIC.items()})
+from ._readout import R_CENTRE, R_METRIC, R_SCALAR, R_UCOMP  # noqa: F401  (the kinds' numbers, under this module's name too)
 
 # ColorBrewer RdBu, 11 classes (red = low, blue = high)
 _RDBU11 = ((103, 0, 31), (178, 24, 43), (214, 96, 77), (244, 165, 130), (253, 219, 199), (247, 247, 247), (209, 229, 240),
@@ -96,28 +94,6 @@ class Renderer:
         return self._lut[key]
 
 
-def _i3(v):
-    return (C.c_int32 * 3)(*([int(x) for x in v] + [0] * 3)[:3])
-
-
-def _code(table: dict, name) -> int:
-    """the library's number of a kind or mode given by name (a number passes through)"""
-    return table[name] if isinstance(name, str) else int(name)
-
-
-def _field_grid(flow, f: torch.Tensor, vector: bool, who: str):
-    """the grid descriptor of `f`, which must be laid out like the flow's u (vector) or p; who: the class named in the error"""
-    ref = flow.u if vector else flow.p
-    if tuple(f.shape) != tuple(ref.shape) or f.stride() != ref.stride() or f.dtype != ref.dtype:
-        raise ValueError(f"{who}: the field must have the layout of flow.{'u' if vector else 'p'} (use waterlily_amd.sim.like)")
-    return S._grid_of(f, flow.D)
-
-
-def _extent(r: Renderer):
-    """the undecomposed extents, ghosts included"""
-    return tuple(int(x) for x in r.flow.N)
-
-
 def project(r: Renderer, f: torch.Tensor, kind="scalar", mode: str = "slice", axis: int = 2, index: Optional[int] = None, box=None,
             i: int = 0, par=None, par2=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The image of `f` reduced along `axis` inside `box` = (lo, hi) (default: inside()): a device view [nb, na] of Float64.
@@ -127,31 +103,28 @@ def project(r: Renderer, f: torch.Tensor, kind="scalar", mode: str = "slice", ax
     magnitude), "sum", "mean".  out: the Float64 buffer the image goes to (default: the object's image; image() renders the body mask into
     the object's second one).  On a z-slab the view holds this rank's rows (axis 0, 1) or its partial image (axis 2)."""
     D = r.flow.D
-    k = _code(_KIND, kind)
-    g = _field_grid(r.flow, f, k != R_SCALAR, "Renderer")
-    n = _extent(r)
+    v = R.Value(kind, i, par, par2)
+    g = R.field_grid(r.flow, f, v.kind != R_SCALAR, "Renderer")
     axis = int(axis)
     if D == 2 and axis != 2:
         raise ValueError("Renderer: a 2-D flow is viewed along axis 2")
     if axis < 0 or axis > 2:
         raise ValueError("Renderer: axis must be 0, 1 or 2")
-    lo = [1] * D if box is None else [int(x) for x in box[0]]
-    hi = [x - 1 for x in n] if box is None else [int(x) for x in box[1]]
+    lo, hi = ([int(x) for x in side] for side in (R.inside(r.flow.N) if box is None else (box[0], box[1])))      # (N: undecomposed)
     if mode == "slice":
         if D == 3:
             if index is None:
                 raise ValueError('Renderer: mode="slice" needs index, the plane along the axis')
             lo[axis], hi[axis] = int(index), int(index) + 1
-        m = _MODE["max"]
+        m = R.MODE["max"]
     else:
-        m = _MODE[mode]
+        m = R.MODE[mode]
     a, b = (1 if axis == 0 else 0), (1 if axis == 2 else 2)
     na, nb = hi[a] - lo[a], hi[b] - lo[b]
     if na < 0 or nb < 0 or na * nb > r.maxpix:
         raise ValueError("Renderer: bad box")
     out = r.img if out is None else out
-    check(_lib.lib().wl_render_project(S._WLT[S._T(f)], C.byref(g), S._ptr(f), k, int(i), None if par is None else _lib.d3(par),
-                                       None if par2 is None else _lib.d3(par2), axis, m, _i3(lo), _i3(hi), S._ptr(out), na))
+    check(_lib.lib().wl_render_project(S._WLT[S._T(f)], C.byref(g), S._ptr(f), *v.flat(), axis, m, R.i3(lo), R.i3(hi), S._ptr(out), na))
     view = out[:na * nb].view(nb, na)
     sl = r.flow.layout.slab
     if sl is not None and axis != 2:                       # this rank's rows: the planes of the box it owns
@@ -233,7 +206,8 @@ def image(r: Renderer, sim, what="omega_mag", mode: str = "max", axis: int = 2, 
 
 # --------------------------------------------------------------------------- recording
 
-def _drain_one(r: Renderer) -> None:
+def drain_one(r: Renderer) -> None:
+    """wait for the oldest frame's copy and move it to r.frames (r: a Renderer, or a Scene, which has the same ring)"""
     slot = r.tail % r.ring
     r.events[slot].synchronize()
     shp = r.shapes[slot]
@@ -246,7 +220,7 @@ def record(r: Renderer, sim, what="curl", **kw) -> None:
     """Render one frame (image()'s arguments) into the next slot of the ring and start its copy into the slot's pinned host twin
     behind an event.  It waits for nothing unless the ring is full: then the oldest frame is drained to r.frames first."""
     if r.head - r.tail >= r.ring:
-        _drain_one(r)
+        drain_one(r)
     slot = r.head % r.ring
     rgba = image(r, sim, what, out=r.ring_dev[slot], **kw)
     n = rgba.numel()
@@ -259,7 +233,7 @@ def record(r: Renderer, sim, what="curl", **kw) -> None:
 def drain(r: Renderer) -> List[np.ndarray]:
     """wait for every copy in flight; all frames recorded so far, oldest first (host arrays [h, w, 4])"""
     while r.tail < r.head:
-        _drain_one(r)
+        drain_one(r)
     return r.frames
 
 
@@ -372,13 +346,8 @@ def gather(img, axis: int, mode: str, slab=None):
     1: the rows concatenated in rank order, the undecomposed image bit for bit.  axis 2: max, min, absmax combined in rank
     order (exact); sum and mean partials added in ascending rank order (a reordered sum: within nz 2^-53 sum|x| of the
     undecomposed one)."""
-    h = img.detach().cpu().numpy().copy() if isinstance(img, torch.Tensor) else np.asarray(img)
-    if slab is None or slab.size == 1:
-        return h
-    import torch.distributed as dist
-    parts = [None] * slab.size
-    dist.all_gather_object(parts, h)
-    if slab.rank != 0:
+    parts, root = _series.host_parts(img, slab)
+    if not root:
         return None
     if int(axis) != 2:
         return np.concatenate(parts, axis=0)

@@ -34,7 +34,7 @@ from . import _lib
 from . import render
 from . import sim as S
 from ._lib import check
-from .downsample import _DevBuf
+from ._readout import DevBuf
 from .mesh import MeshBody
 from .render import drain, write_apng, write_png  # noqa: F401  (drain(sc): every recorded frame, as for a Renderer)
 
@@ -159,10 +159,10 @@ class Scene:
         self.device = _device(getattr(flow_or_device, "device", flow_or_device))
         self.W, self.H, self.ssaa, self.ring = W, H, ssaa, int(ring)
         self.Wi, self.Hi = W * ssaa, H * ssaa
-        self._key = _DevBuf(8 * self.Wi * self.Hi)
-        self._rgba = _DevBuf(4 * self.Wi * self.Hi)
-        self._out = _DevBuf(4 * W * H)
-        self._scratch = _DevBuf(16)
+        self._key = DevBuf(8 * self.Wi * self.Hi)
+        self._rgba = DevBuf(4 * self.Wi * self.Hi)
+        self._out = DevBuf(4 * W * H)
+        self._scratch = DevBuf(16)
         nb = W * H * 4
         self.ring_dev = torch.zeros((self.ring, nb), dtype=torch.uint8, device=self.device)
         self.ring_host = torch.zeros((self.ring, nb), dtype=torch.uint8).pin_memory()
@@ -236,7 +236,7 @@ def draw(sc: Scene, cam, tri: torch.Tensor, val: Optional[torch.Tensor] = None, 
     need = C.c_int64()
     check(_lib.lib().wl_scene_scratch(nt, C.byref(need)))
     if sc._scratch.nbytes < need.value:
-        sc._scratch = _DevBuf(need.value)                      # (wl_free waits for the device: the old block outlives its last use)
+        sc._scratch = DevBuf(need.value)                      # (wl_free waits for the device: the old block outlives its last use)
     d = _Draw(nt=nt, base=base, tri=tri, val=val, M=_m16(M), clims=clims, lut=sc.lut(cmap) if val is not None else None, levels=int(levels),
               color=_u8(color), ambient=float(ambient), light=_lib.d3(light), nan_rgba=_u8(nan_rgba))
     check(_lib.lib().wl_scene_draw(C.c_void_p(sc._key.ptr), sc.Wi, sc.Hi, d.M, S._ptr(tri) if nt else None, nt, base, int(large_px),
@@ -267,7 +267,7 @@ def record(sc: Scene, background=(255, 255, 255, 255)) -> None:
     """frame() into the next slot of the ring, and the start of its copy into the slot's pinned host twin behind an event.  It
     waits for nothing unless the ring is full: then the oldest frame is drained to sc.frames first."""
     if sc.head - sc.tail >= sc.ring:
-        render._drain_one(sc)
+        render.drain_one(sc)
     slot = sc.head % sc.ring
     rgba = frame(sc, background, out=sc.ring_dev[slot])
     sc.ring_host[slot].copy_(sc.ring_dev[slot], non_blocking=True)

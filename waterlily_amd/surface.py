@@ -32,6 +32,7 @@ from ._lib import check
 from .mesh import MeshBody
 from ._series import _rank_sum
 from .stats import weight
+from .vtk import data_array
 
 COLUMNS = tuple(f"{k}_{a}" for k in ("Fp", "Fv", "Mp", "Mv") for a in "xyz")
 
@@ -144,14 +145,6 @@ def loads(sim, delta=None, x0=None) -> Dict[str, float]:
     return dict(zip(COLUMNS, (float(x) for x in series(sl)[1][0])))
 
 
-def _data_array(name: str, a: np.ndarray, vtk_type: str) -> str:
-    a = np.asarray(a)
-    nc = 1 if a.ndim == 1 else a.shape[1]
-    fmt = "%d" if vtk_type.startswith("Int") else "%.17g"
-    body = "\n".join(" ".join(fmt % v for v in row) for row in a.reshape(len(a), -1))
-    return f'<DataArray type="{vtk_type}" Name="{name}" NumberOfComponents="{nc}" format="ascii">\n{body}\n</DataArray>\n'
-
-
 def write_vtp(path, sl) -> None:
     """The triangles at the sampled time as a VTK PolyData file (XML, ascii arrays): points = the vertices in x space, cell data =
     p, traction, area_vector, body_velocity and the means when kept.  On z-slabs every rank must call it; rank 0 writes."""
@@ -161,12 +154,12 @@ def write_vtp(path, sl) -> None:
     pts = _to_x(sl.body, sl.body.vertices, sl.time)
     tri = np.asarray(sl.body.triangles, dtype=np.int64)
     nt = len(tri)
-    cells = "".join(_data_array(k, f[k], "Float64") for k in ("p", "traction", "area_vector", "body_velocity", "mean_p", "mean_traction")
+    cells = "".join(data_array(k, f[k], "Float64") for k in ("p", "traction", "area_vector", "body_velocity", "mean_p", "mean_traction")
                     if k in f)
     with open(path, "w") as o:
         o.write('<?xml version="1.0"?>\n<VTKFile type="PolyData" version="1.0" byte_order="LittleEndian">\n<PolyData>\n'
                 f'<Piece NumberOfPoints="{len(pts)}" NumberOfVerts="0" NumberOfLines="0" NumberOfStrips="0" NumberOfPolys="{nt}">\n'
-                "<Points>\n" + _data_array("Points", pts, "Float64") + "</Points>\n"
+                "<Points>\n" + data_array("Points", pts, "Float64") + "</Points>\n"
                 '<CellData Scalars="p" Vectors="traction">\n' + cells + "</CellData>\n"
-                "<Polys>\n" + _data_array("connectivity", tri.ravel(), "Int64") + _data_array("offsets", 3 * np.arange(1, nt + 1), "Int64")
+                "<Polys>\n" + data_array("connectivity", tri.ravel(), "Int64") + data_array("offsets", 3 * np.arange(1, nt + 1), "Int64")
                 + "</Polys>\n</Piece>\n</PolyData>\n</VTKFile>\n")

@@ -29,24 +29,13 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import _readout as R
 from . import _series
-from . import render
 from . import sim as S
 from ._lib import check
-from .downsample import _DevBuf
+from ._readout import Value  # noqa: F401  (one of the two values of a pair: the family's one descriptor of a cell's value)
 
 COLS, MAX_LINE = 10, 1024
-
-
-class Value:
-    """One of the two values of a pair.  kind: "scalar" (a scalar field), "ucomp" / "centre" (component i of a vector field, as
-    stored / averaged to the cell centre) or a metric of u: "ke", "curl", "omega_mag", "omega_theta", "lambda2" (i, par, par2
-    as waterlily_amd.sim.metric): the kinds of hist.Axis.  absval: |v| in place of v -- read by Regions, which shares this
-    descriptor; TwoPoint refuses it."""
-
-    def __init__(self, kind="scalar", i: int = 0, par=None, par2=None, absval: bool = False):
-        self.kind, self.i, self.par, self.par2 = render._code(render._KIND, kind), int(i), par, par2
-        self.absval = bool(absval)
 
 
 class TwoPoint:
@@ -65,14 +54,8 @@ class TwoPoint:
         sl = flow.layout.slab
         if self.axis == 2 and sl is not None and sl.size > 1:
             raise ValueError("TwoPoint: axis 2 of a flow decomposed along z: the lines cross ranks")
-        N = tuple(int(x) for x in flow.N)
-        self.box = None
-        lo, hi = (1,) * self.D, tuple(n - 1 for n in N)
-        if box is not None:
-            lo, hi = tuple(int(x) for x in box[0]), tuple(int(x) for x in box[1])
-            if len(lo) != self.D or len(hi) != self.D or any(not (0 <= l < h <= n - 1) for l, h, n in zip(lo, hi, N)):
-                raise ValueError(f"TwoPoint: a box is (lo, hi) with {self.D} entries each, 0 <= lo < hi <= n - 1")
-            self.box = (lo, hi)
+        (lo, hi), given = R.box_of("TwoPoint", tuple(int(x) for x in flow.N), box)
+        self.box = (lo, hi) if given else None
         self.n = hi[self.axis] - lo[self.axis]
         if self.n > MAX_LINE:
             raise ValueError(f"TwoPoint: the box is longer than {MAX_LINE} cells along the axis")
@@ -80,23 +63,12 @@ class TwoPoint:
         if not 1 <= self.nsep <= self.n:
             raise ValueError(f"TwoPoint: nsep is 1..{self.n}, the box's extent along the axis")
         self._grid = flow.layout.grid()
-        self._val = {name: self._value(x) for name, x in (("a", a), ("b", b)) if x is not None}
+        self._val = {name: x.fill(_lib.TpValue()) for name, x in (("a", a), ("b", b)) if x is not None}
         nb = C.c_int64()
-        blo, bhi = self._box()
+        blo, bhi = R.box_args(self.box)
         check(_lib.lib().wl_twopoint_scratch(C.byref(self._grid), self.axis, self.nsep, blo, bhi, C.byref(nb)))
-        self._scratch = _DevBuf(nb.value)
-        self._tab = _DevBuf(8 * COLS * self.nsep)
-
-    @staticmethod
-    def _value(x: Value) -> _lib.TpValue:
-        s = _lib.TpValue()
-        s.kind, s.ipar = x.kind, x.i
-        s.par[:] = list(_lib.d3((0, 0, 0) if x.par is None else x.par))
-        s.par2[:] = list(_lib.d3((0, 0, 0) if x.par2 is None else x.par2))
-        return s
-
-    def _box(self):
-        return (None, None) if self.box is None else (render._i3(self.box[0]), render._i3(self.box[1]))
+        self._scratch = R.DevBuf(nb.value)
+        self._tab = R.DevBuf(8 * COLS * self.nsep)
 
 
 def measure(tp: TwoPoint, fa: torch.Tensor, fb: Optional[torch.Tensor] = None, accumulate: bool = False) -> torch.Tensor:
@@ -112,11 +84,11 @@ def measure(tp: TwoPoint, fa: torch.Tensor, fb: Optional[torch.Tensor] = None, a
             continue
         if S._T(f) != np.dtype(tp.flow.T):
             raise ValueError("TwoPoint: the fields must have the flow's dtype")
-        render._field_grid(tp.flow, f, x.kind != render.R_SCALAR, "TwoPoint")
+        R.field_grid(tp.flow, f, x.kind != R.R_SCALAR, "TwoPoint")
     tp._val["a"].f = fa.data_ptr()
     if tp.b is not None:
         tp._val["b"].f = fb.data_ptr()
-    lo, hi = tp._box()
+    lo, hi = R.box_args(tp.box)
     check(_lib.lib().wl_twopoint(S._WLT[S._T(fa)], C.byref(tp._grid), C.byref(tp._val["a"]), C.byref(tp._val["b"]) if tp.b is not None else None,
                                  tp.axis, tp.nsep, int(tp.periodic), lo, hi, int(bool(accumulate)), C.c_void_p(tp._scratch.ptr),
                                  tp._scratch.nbytes, C.c_void_p(tp._tab.ptr)))
@@ -232,8 +204,5 @@ def combine(parts) -> np.ndarray:
 def gather(tab, slab=None):
     """The ranks' tables added in rank order on rank 0 as a host array (None on the other ranks; every rank must call it).
     Column 0 is exact; the sums are the decomposed sums, not the undecomposed bits (combine)."""
-    v = tab.detach().cpu().numpy().copy() if isinstance(tab, torch.Tensor) else np.asarray(tab)
-    parts = _series._rank_parts(v, slab)
-    if slab is not None and slab.size > 1 and slab.rank != 0:
-        return None
-    return combine(parts)
+    parts, root = _series.host_parts(tab, slab)
+    return combine(parts) if root else None

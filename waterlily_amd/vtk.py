@@ -206,6 +206,15 @@ def _pvti(wext, arrays, pieces) -> bytes:
     return "\n".join(out).encode()
 
 
+def data_array(name: str, a: np.ndarray, vtk_type: str) -> str:
+    """an ascii <DataArray> of a PolyData file (surface.write_vtp, iso.write_vtp): one row of `a` per line"""
+    a = np.asarray(a)
+    nc = 1 if a.ndim == 1 else a.shape[1]
+    fmt = "%d" if vtk_type.startswith("Int") else "%.17g"
+    body = "\n".join(" ".join(fmt % v for v in row) for row in a.reshape(len(a), -1))
+    return f'<DataArray type="{vtk_type}" Name="{name}" NumberOfComponents="{nc}" format="ascii">\n{body}\n</DataArray>\n'
+
+
 def _take_slot(w: VTKWriter, nbytes: int, device, zero: bool = False) -> Optional[_Slot]:
     """The device staging slot of the next snapshot, at least `nbytes` large, marked busy, with the worker running; None when
     on_busy == "skip" dropped the snapshot.  zero: a newly made slot starts as zeros (a writer that leaves padding untouched)."""
