@@ -659,6 +659,55 @@ int wl_scene_shade(const uint64_t *key_dev, int W, int H, uint32_t base, int64_t
 int wl_scene_resolve(const uint8_t *rgba_dev, int W, int H, const uint64_t *key_dev, int ssaa, const uint8_t background_rgba[4],
                      uint8_t *out_dev);
 
+/* ------------------------------------------------------------------ ray-marched pictures of a scalar field (Volume, waterlily_amd/volume.py)
+ * The field itself seen through Scene's camera: a scalar field f in the flow's layout (p, sigma, a `like` scratch) as an
+ * emitting and absorbing cloud, composited front to back over what wl_scene_draw and wl_scene_shade left in key_dev and rgba_dev
+ * (both W x H, the draw's size), so that a surface hides the cloud behind it.  wl_scene_volume runs after the last
+ * wl_scene_shade and before wl_scene_average, which takes wl_scene_resolve's place in such a picture.  Every double operation
+ * below is its own IEEE operation in the order written, and there is no sqrt and no transcendental: acc_dev and rgba_dev are a
+ * function of the field, the keys and the camera alone, bit for bit (tests/volume_ref.py restates all of it).
+ *   ray     : pixel (i, j) (column, row; row 0 is the top, as for wl_scene_draw): x_n = ((i + 0.5)/W)*2 - 1, y_n = 1 - ((j + 0.5)/H)*2;
+ *             h0_r = (Minv[r][0]*x_n + Minv[r][1]*y_n) + Minv[r][3] and g_r = Minv[r][2], r = 0..3, Minv the inverse of the draw's
+ *             M (row-major, made on the host).  The homogeneous point at NDC depth z is h_r(z) = h0_r + z*g_r and the world
+ *             point P(z)_d = h_d(z) / h_3(z).  P0 = P(0), P1 = P(1), D = P1 - P0.  A ray with a component of P0 or P1 that is
+ *             not finite is empty.  The parameter s in [0, 1] of P0 + s D is linear in eye depth along EVERY ray (perspective
+ *             included), so the samples of all rays lie on common planes parallel to the picture plane: view-aligned slices.
+ *             An oblique ray of a wide perspective therefore walks 1/cos(theta) more world length per step than the central
+ *             one; no sqrt is spent on equalising that.
+ *   box     : the cells lo_d <= J_d < hi_d (0-based; NULL, NULL: inside()), hi_d - lo_d >= 2.  The frame is x = J - 0.5 (Scene's
+ *             and MeshBody's) and X = x + 1.5 in wl_interp's coordinates.  The sampled region is the cell CENTRES of the box:
+ *             blo_d = lo_d - 0.5, bhi_d = hi_d - 1.5.  s_in = 0, s_out = 1; for d = 0, 1, 2: when D_d == 0 the ray is empty unless
+ *             blo_d <= P0_d <= bhi_d; otherwise ta = (blo_d - P0_d)/D_d, tb = (bhi_d - P0_d)/D_d, s_in = max(s_in, min(ta, tb)),
+ *             s_out = min(s_out, max(ta, tb)) (max(a, b) = a > b ? a : b, min likewise).
+ *   surface : a pixel whose key is not "nothing": zq = key >> 32, z = (double)zq / 2^32, Ps = P(z), s_stop = (((Ps_0-P0_0)*D_0 +
+ *             (Ps_1-P0_1)*D_1) + (Ps_2-P0_2)*D_2) / ((D_0*D_0 + D_1*D_1) + D_2*D_2); otherwise s_stop = +inf.
+ *   samples : k = 0, 1, ... while s_k = ((double)k + 0.5)*ds satisfies s_k <= s_out and s_k < s_stop; the sample is taken when
+ *             s_k >= s_in (an implementation may start at any k not beyond the first taken one).  Pk_d = P0_d + s_k*D_d;
+ *             v = wl_interp's value of f at Pk + 1.5 (a corner of weight 0 is not read, a weighted corner outside the array
+ *             gives NaN); a NaN v is skipped.  idx by wl_render_shade's rule from (v, vmin, vmax, levels); a = opac_dev[idx];
+ *             w = T*a; C_c = C_c + w*(double)lut_dev[idx][c], c = 0, 1, 2; T = T*(1.0 - a); when T < t_min the march of that
+ *             ray stops with T kept as it is.  C = 0, T = 1 at the start.
+ *   pixel   : base = background_rgba when the key is "nothing", otherwise rgba_dev's pixel.  A colour channel becomes
+ *             floor((C_c + T*(double)base_c) + 0.5) clamped to 0..255, alpha floor(((1.0 - T)*255.0 + T*(double)base_a) + 0.5)
+ *             clamped, written in place for EVERY pixel: an empty ray writes base exactly, so afterwards rgba_dev holds the
+ *             background too and the keys are no longer needed to finish the picture.  acc_dev[H*W*4], when given, gets
+ *             C_r, C_g, C_b, T.  key_dev is only read.
+ *   average : wl_scene_average is wl_scene_resolve's block average, (sum + n/2) / n per channel in integers, without the key
+ *             test (one device function serves both).
+ * opac_dev: 256 doubles in [0, 1], the share absorbed per step; its values are the caller's and are not checked on the device.
+ * How tiles of pixels are dealt to wavefronts, and the skip of a sample whose a == 0 before its colour is fetched, show in no
+ * bit.  Refused with WL_E_ARG before the device is touched: a NULL g, f, Minv, lut_dev, opac_dev, key_dev, background_rgba or
+ * rgba_dev; an unknown dtype; D != 3; a bad box, only one of lo and hi, or an extent below 2; a Minv entry that is not finite;
+ * ds outside [2^-20, 1]; vmin >= vmax or either not finite; levels outside 0..256; t_min outside [0, 1); W or H outside
+ * 1..WL_SCENE_MAX_SIZE; a frame that is not 4-byte, keys or acc_dev that are not 8-byte aligned; for wl_scene_average: ssaa
+ * other than 1, 2, 4 or not dividing W and H, or an unaligned frame or output.  A z-slab grid is refused with WL_E_STATE: it
+ * has no distributed picture, as for Scene.  Asynchronous on the library's stream; nothing is allocated, no LDS, no float
+ * atomics.  WaterLily v1.3 draws on the host: these entry points are there for a later binding. */
+int wl_scene_volume(wl_dtype t, const wl_grid *g, const void *f, const double Minv[16], double ds, const int32_t lo[3], const int32_t hi[3],
+                    double vmin, double vmax, int levels, const uint8_t *lut_dev, const double *opac_dev, double t_min,
+                    const uint64_t *key_dev, const uint8_t background_rgba[4], uint8_t *rgba_dev, double *acc_dev, int W, int H);
+int wl_scene_average(const uint8_t *rgba_dev, int W, int H, int ssaa, uint8_t *out_dev);
+
 /* ------------------------------------------------------------------ box-filtered, cropped volumes (Downsampler, waterlily_amd/downsample.py)
  * The 3-D counterpart of wl_render_project: the fine cells lo_d <= J_d < hi_d (0-based, z global) are cut into blocks of
  * factor^D cells and every block becomes one coarse cell, its value formed on the fly from f.  No volume is filled first: a

@@ -16,3 +16,4 @@ from . import scene  # noqa: F401
 from .scene import Camera, Scene  # noqa: F401
 from . import twopoint  # noqa: F401
 from .twopoint import TwoPoint, Value  # noqa: F401
+from . import volume  # noqa: F401

@@ -268,6 +268,8 @@ def lib() -> C.CDLL:
         "wl_scene_draw": (i, [vp, i, i, dp, vp, i64, C.c_uint32, i64, vp, i64]),
         "wl_scene_shade": (i, [vp, i, i, C.c_uint32, i64, vp, vp, dp, d, d, i, vp, C.POINTER(C.c_uint8), dp, d, C.POINTER(C.c_uint8), vp]),
         "wl_scene_resolve": (i, [vp, i, i, vp, i, C.POINTER(C.c_uint8), vp]),
+        "wl_scene_volume": (i, [i, gp, vp, dp, d, C.POINTER(C.c_int32), C.POINTER(C.c_int32), d, d, i, vp, vp, d, vp, vp, vp, vp, i, i]),
+        "wl_scene_average": (i, [vp, i, i, i, vp]),
         "wl_downsample": (i, [i, gp, vp, i, i, dp, dp, i, i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), i, vp, i, i]),
         "wl_downsample_extent": (i, [gp, i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
         "wl_histogram": (i, [i, gp, vp, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), i, vp]),      # (a, b: byref(HistAxis))

@@ -28,6 +28,7 @@
 #include "wl_regions.h"
 #include "wl_region_sums.h"
 #include "wl_scene.h"
+#include "wl_volume.h"
 
 namespace wl {
 
@@ -1812,6 +1813,51 @@ int wl_scene_resolve(const uint8_t *rgba_dev, int W, int H, const uint64_t *key_
     const uint32_t bg = (uint32_t)background_rgba[0] | ((uint32_t)background_rgba[1] << 8) | ((uint32_t)background_rgba[2] << 16) |
                         ((uint32_t)background_rgba[3] << 24);
     return op_scene_resolve(rgba_dev, (const unsigned long long *)key_dev, W, H, ssaa, bg, out_dev);
+}
+int wl_scene_volume(wl_dtype t, const wl_grid *g, const void *f, const double Minv[16], double ds, const int32_t lo[3], const int32_t hi[3],
+                    double vmin, double vmax, int levels, const uint8_t *lut_dev, const double *opac_dev, double t_min,
+                    const uint64_t *key_dev, const uint8_t background_rgba[4], uint8_t *rgba_dev, double *acc_dev, int W, int H) {
+    const char *who = "wl_scene_volume";
+    if (!g || !f || !Minv || !lut_dev || !opac_dev || !key_dev || !background_rgba || !rgba_dev)
+        WL_BAD(who, "null grid, field, inverse camera, colour table, opacity table, keys, background or frame");
+    WL_TRY(check_grid(g));
+    WL_TRY(check_dtype(who, t));
+    if (g->D != 3) WL_BAD(who, "a volume needs D == 3");
+    if (g->nzg > 0) return fail(WL_E_STATE, "wl_scene_volume: a z-slab decomposition has no distributed picture", __FILE__, __LINE__);
+    const G gg = mkG(g);
+    int l[3], h[3];
+    WL_TRY(parse_box(who, gg, 3, 1, false, lo, hi, l, h));
+    for (int d = 0; d < 3; ++d)
+        if (h[d] - l[d] < 2) WL_BAD(who, "the box needs two cells or more in every direction (hi - lo >= 2)");
+    VolumeArgs A;
+    for (int k = 0; k < 16; ++k) {
+        if (!std::isfinite(Minv[k])) WL_BAD(who, "the inverse camera matrix must be finite");
+        A.mi[k] = Minv[k];
+    }
+    if (!(ds >= 1.0 / 1048576.0 && ds <= 1.0)) WL_BAD(who, "the step ds must lie in [2^-20, 1]");
+    if (!(std::isfinite(vmin) && std::isfinite(vmax) && vmin < vmax)) WL_BAD(who, "need finite vmin < vmax");
+    if (levels < 0 || levels > 256) WL_BAD(who, "levels must lie in 0..256");
+    if (!(t_min >= 0.0 && t_min < 1.0)) WL_BAD(who, "t_min must lie in [0, 1)");
+    WL_TRY(scene_size(who, W, H));
+    if (((uintptr_t)rgba_dev & 3u) != 0 || ((uintptr_t)key_dev & 7u) != 0 || ((uintptr_t)acc_dev & 7u) != 0)
+        WL_BAD(who, "the frame must be 4-byte aligned, the keys and acc_dev 8-byte aligned");
+    A.ds = ds; A.vmin = vmin; A.vmax = vmax; A.t_min = t_min; A.W = W; A.H = H; A.levels = levels;
+    for (int d = 0; d < 3; ++d) {
+        A.blo[d] = (double)l[d] - 0.5;
+        A.bhi[d] = (double)h[d] - 1.5;
+    }
+    A.bg = (uint32_t)background_rgba[0] | ((uint32_t)background_rgba[1] << 8) | ((uint32_t)background_rgba[2] << 16) |
+           ((uint32_t)background_rgba[3] << 24);
+    WL_DISPATCH_T(t, (op_scene_volume<T>(gg, A, (const T *)f, lut_dev, opac_dev, (const unsigned long long *)key_dev, rgba_dev, acc_dev)));
+}
+int wl_scene_average(const uint8_t *rgba_dev, int W, int H, int ssaa, uint8_t *out_dev) {
+    const char *who = "wl_scene_average";
+    if (!rgba_dev || !out_dev) WL_BAD(who, "null frame or output");
+    if ((((uintptr_t)rgba_dev | (uintptr_t)out_dev) & 3u) != 0) WL_BAD(who, "frame and output must be 4-byte aligned");
+    WL_TRY(scene_size(who, W, H));
+    if (ssaa != 1 && ssaa != 2 && ssaa != 4) WL_BAD(who, "bad ssaa (1, 2 or 4)");
+    if (W % ssaa != 0 || H % ssaa != 0) WL_BAD(who, "W and H must be multiples of ssaa");
+    return op_scene_average(rgba_dev, W, H, ssaa, out_dev);
 }
 // the checks wl_downsample and wl_downsample_extent share: factor and box -> l, h (a box without cells is refused here)
 static int downsample_box(const char *who, const wl_grid *g, const G &gg, int factor, const int32_t lo[3], const int32_t hi[3], int l[3], int h[3]) {

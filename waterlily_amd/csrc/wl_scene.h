@@ -216,20 +216,27 @@ __global__ __launch_bounds__(256) void k_scene_shade(const SceneCam C, const Sce
     }
     rgba[p] = out;
 }
+// the ssaa x ssaa block average of output pixel (i, j): per channel (sum + n/2) / n in integers.  KEYED: a pixel whose key is
+// "nothing" counts as bg (wl_scene_resolve); otherwise every pixel counts as it is (wl_scene_average, wl_volume.h)
+template <bool KEYED>
+__device__ __forceinline__ uint32_t scene_block_average(const uint32_t *__restrict__ rgba, const unsigned long long *__restrict__ key, int W,
+                                                        int ssaa, uint32_t bg, int i, int j) {
+    unsigned s0 = 0, s1 = 0, s2 = 0, s3 = 0;
+    for (int b = 0; b < ssaa; ++b)
+        for (int a = 0; a < ssaa; ++a) {
+            const long p = (long)(j * ssaa + b) * W + (i * ssaa + a);
+            const uint32_t c = (KEYED && key[p] == SCENE_NOTHING) ? bg : rgba[p];
+            s0 += c & 0xFFu; s1 += (c >> 8) & 0xFFu; s2 += (c >> 16) & 0xFFu; s3 += c >> 24;
+        }
+    const unsigned n = (unsigned)(ssaa * ssaa), h = n / 2;
+    return ((s0 + h) / n) | (((s1 + h) / n) << 8) | (((s2 + h) / n) << 16) | (((s3 + h) / n) << 24);
+}
 __global__ __launch_bounds__(256) void k_scene_resolve(const uint32_t *__restrict__ rgba, const unsigned long long *__restrict__ key, int W,
                                                       int H, int ssaa, uint32_t bg, uint32_t *__restrict__ out) {
     const int ow = W / ssaa, oh = H / ssaa;
     const int i = (int)blockIdx.x * 64 + (int)(threadIdx.x & 63), j = (int)blockIdx.y * 4 + (int)(threadIdx.x >> 6);
     if (i >= ow || j >= oh) return;
-    unsigned s0 = 0, s1 = 0, s2 = 0, s3 = 0;
-    for (int b = 0; b < ssaa; ++b)
-        for (int a = 0; a < ssaa; ++a) {
-            const long p = (long)(j * ssaa + b) * W + (i * ssaa + a);
-            const uint32_t c = key[p] == SCENE_NOTHING ? bg : rgba[p];
-            s0 += c & 0xFFu; s1 += (c >> 8) & 0xFFu; s2 += (c >> 16) & 0xFFu; s3 += c >> 24;
-        }
-    const unsigned n = (unsigned)(ssaa * ssaa), h = n / 2;
-    out[(long)j * ow + i] = ((s0 + h) / n) | (((s1 + h) / n) << 8) | (((s2 + h) / n) << 16) | (((s3 + h) / n) << 24);
+    out[(long)j * ow + i] = scene_block_average<true>(rgba, key, W, ssaa, bg, i, j);
 }
 
 // ------------------------------------------------------------------------------------------ launches

@@ -128,6 +128,10 @@ class Camera:
             P[3, 3] = 1.0
         return np.ascontiguousarray(P @ V)
 
+    def inverse(self, W: int, H: int) -> np.ndarray:
+        """the inverse of matrix(W, H): what wl_scene_volume makes its rays from"""
+        return np.linalg.inv(self.matrix(W, H))
+
 
 def _device(d) -> torch.device:
     """a torch device with its index ("cuda" is the current one), so that it compares equal to a tensor's"""
@@ -172,6 +176,8 @@ class Scene:
         self.tail = 0
         self.frames: List[np.ndarray] = []
         self.draws: List[_Draw] = []
+        self.volume = None                                     # the picture's queued volume (waterlily_amd.volume.add)
+        self._vfield = None                                    # volume.metric's scratch scalar field
         self._lut = {}
         self._cleared = False
 
@@ -199,6 +205,7 @@ def clear(sc: Scene) -> None:
     """Start a picture: every key becomes "nothing" and the list of draws is emptied."""
     check(_lib.lib().wl_scene_clear(C.c_void_p(sc._key.ptr), sc.Wi, sc.Hi))
     sc.draws = []
+    sc.volume = None
     sc._cleared = True
 
 
@@ -246,7 +253,8 @@ def draw(sc: Scene, cam, tri: torch.Tensor, val: Optional[torch.Tensor] = None, 
 
 def frame(sc: Scene, background=(255, 255, 255, 255), out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Shade every draw's pixels, fill the rest with `background`, average ssaa x ssaa blocks: the RGBA uint8 device view
-    [H, W, 4] of `out` (default: the object's frame, which the next frame() overwrites)."""
+    [H, W, 4] of `out` (default: the object's frame, which the next frame() overwrites).  A queued volume (waterlily_amd.volume.add)
+    is composited over the shaded frame and the background before the average."""
     if not sc._cleared:
         raise ValueError("Scene: clear() starts a picture")
     L = _lib.lib()
@@ -259,7 +267,12 @@ def frame(sc: Scene, background=(255, 255, 255, 255), out: Optional[torch.Tensor
     dst = sc._out.tensor(torch.uint8, sc.device) if out is None else out
     if dst.numel() < n or dst.dtype != torch.uint8 or not dst.is_contiguous():
         raise ValueError("Scene: the output must be a contiguous uint8 tensor of H*W*4 elements or more")
-    check(L.wl_scene_resolve(C.c_void_p(sc._rgba.ptr), sc.Wi, sc.Hi, C.c_void_p(sc._key.ptr), sc.ssaa, _u8(background), S._ptr(dst)))
+    if sc.volume is not None:                                  # the cloud over the shaded frame and the background, then the plain average
+        from . import volume
+        volume.run(sc, _u8(background))
+        check(L.wl_scene_average(C.c_void_p(sc._rgba.ptr), sc.Wi, sc.Hi, sc.ssaa, S._ptr(dst)))
+    else:
+        check(L.wl_scene_resolve(C.c_void_p(sc._rgba.ptr), sc.Wi, sc.Hi, C.c_void_p(sc._key.ptr), sc.ssaa, _u8(background), S._ptr(dst)))
     return dst.reshape(-1)[:n].view(sc.H, sc.W, 4)
 
 
